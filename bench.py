@@ -18,7 +18,15 @@ Weak scaling: every rank owns reads_per_gpu records of one global dataset
 Workloads (--workload): C2 (default; BASELINE configs[1]) = 10M reads per GPU, weak
 scaling; C4 (configs[3]) = 500M reads in all, 500M/N per GPU, strong scaling.
 
-Usage: python bench.py [--gpus N --steps K --warmup W] [--workload C2|C4]
+A plain run sets up, warms up, times the K steps (the score and assign launches of every
+4th step carry their own timing, for `roofline`) and prints the line. --full adds, after
+the timed steps: the sustained run, the per-kernel breakdown and the isolated score kernel
+(`sustained`, `kernels_us`, `kernels_per_step`, `roofline.dominant` / `.isolated`), the C3,
+C3 k16 and H5 workloads, the host end-to-end path and the CPU baselines. --dump-outputs DIR
+writes what the last timed step computed (see dump_outputs) for output-for-output
+comparison of two builds: the inputs are seeded, identical from run to run.
+
+Usage: python bench.py [--gpus N --steps K --warmup W] [--workload C2|C4] [--full] [--dump-outputs DIR]
        torchrun --nproc-per-node N bench.py --gpus N ...
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts the N ranks itself
 (rogtk_amd.launch: spawned processes, one per GPU, before anything touches the GPU).
@@ -129,7 +137,43 @@ def parse():
                     help="skip the H5 block (every group of a 10M-read C3-style run assembled: GPU spectra + "
                          "host assembly threads, round 6)")
     ap.add_argument("--h5-reads", type=int, default=10_000_000)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the line can report: the sustained run, "
+                         "the per-kernel breakdown and the isolated score kernel, the C3 / C3 k16 / H5 workloads, "
+                         "the host end-to-end path and the CPU baselines (each still has its own --no-... switch). "
+                         "Without it those keys of the line are null / empty")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the 7 H1 fields, the H2 "
+                         "within bits and the H3 cluster ids of a fixed seeded sample of rows, and the engine's "
+                         "counts) as DIR/<name>.npy, float64")
     return ap.parse_args()
+
+
+DUMP_ROWS = 500_000  # rows of the --dump-outputs sample: 10 float64 arrays of it are 40 MB
+
+
+def dump_outputs(out_dir: str, slot, count: int, rank: int, world: int) -> None:
+    """--dump-outputs: the outputs a caller of the timed path receives from `slot` (the last
+    timed step's, final after drain()), as float64 .npy files: every row when the batch has
+    at most DUMP_ROWS rows, else a seeded sample of DUMP_ROWS rows (their indices in rows.npy),
+    the same rows on every run. Ranks other than 0 of a multi-GPU run add a _rank<r> suffix."""
+    os.makedirs(out_dir, exist_ok=True)
+    if count > DUMP_ROWS:
+        rows_h = np.sort(np.random.default_rng(20240229).choice(count, size=DUMP_ROWS, replace=False))
+    else:
+        rows_h = np.arange(count, dtype=np.int64)
+    rows = torch.from_numpy(rows_h).to(slot.cid.device)
+    out = {"rows": rows_h.astype(np.float64)}
+    for f, t in slot.scores.items():
+        out[f] = t[:count][rows].cpu().numpy().astype(np.float64)
+    out["cluster_id"] = slot.cid[:count][rows].cpu().numpy().view(np.uint32).astype(np.float64)
+    bits = np.unpackbits(slot.within.cpu().numpy().view(np.uint8), bitorder="little")[:count]
+    out["hamming_within"] = bits[rows_h].astype(np.float64)
+    st = slot.eng.stats()
+    out["cluster_stats"] = np.array([st["n_distinct"], st["n_clusters"], st["overflow"]], dtype=np.float64)
+    sfx = f"_rank{rank}" if world > 1 and rank else ""
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), a)
 
 
 def emulated_shard_bitmap(n_total: int, r: int, W: int, L: int, dev) -> torch.Tensor:
@@ -626,8 +670,10 @@ def main():
                        mark_stream=args.mark_stream, fused_assign=args.fused_assign, assign_lag=args.assign_lag,
                        split_mark=not args.no_split_mark)
 
+    last = [None]  # the slot of the latest submit
+
     def step():
-        pipe.submit(batch)
+        last[0] = pipe.submit(batch)
 
     for _ in range(args.warmup):
         step()
@@ -688,12 +734,16 @@ def main():
         t = torch.tensor([el], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    if args.dump_outputs:
+        if last[0] is None:
+            raise SystemExit("bench.py: --dump-outputs needs at least one step")
+        dump_outputs(args.dump_outputs, last[0], count, rank, world)
     stats = pipe.slots[0].eng.stats()
     h3_rounds = pipe.slots[0].eng.rounds()  # global hook rounds the last resolve needed
     # Sustained run (outside the timed region): the same steps back to back for a few
     # seconds, all ranks together; reported beside `value` as a steady-state check
     sustained = None
-    if args.sustain_seconds > 0:
+    if args.full and args.sustain_seconds > 0:
         barrier(world)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -717,7 +767,7 @@ def main():
     # for the per-phase breakdown (kernels_us; these steps are not timed).
     breakdown = {}
     per_kernel = {}
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         pipe.drain()  # the window then holds exactly w batches' kernels
         torch.cuda.synchronize()
         D.profile_select(None)
@@ -746,7 +796,7 @@ def main():
     # Outside the timed region: the same score kernel launched alone (nothing else on
     # the GPU), so its duration is the kernel's own, not the pipeline-shared one.
     iso = None
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         slot = pipe.slots[0]
         torch.cuda.synchronize()
         D.profile_reset()
@@ -824,7 +874,7 @@ def main():
                                 "note": "same kernel, same batch, launched alone after the timed region"}
     sort_mark = pipe.sort_mark
     c3 = c3_k16 = None
-    if world == 1 and not args.no_c3 and args.emulate_ranks == 1:
+    if args.full and world == 1 and not args.no_c3 and args.emulate_ranks == 1:
         del pipe, batch, codes
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
@@ -835,13 +885,13 @@ def main():
             # (fracture.rs:246-256), min_coverage 5
             c3_k16 = c3_workload(args.c3_reads, steps=args.c3_steps, warmup=1, k=15, min_coverage=5)
     h5 = None
-    if world == 1 and not args.no_h5 and args.emulate_ranks == 1:
+    if args.full and world == 1 and not args.no_h5 and args.emulate_ranks == 1:
         h5 = h5_workload(args.h5_reads)
     e2e = None
-    if not args.no_end_to_end and args.emulate_ranks == 1:
+    if args.full and not args.no_end_to_end and args.emulate_ranks == 1:
         e2e = end_to_end(codes_h[: min(count, 10_000_000)], L, md)
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(codes_h, L, md, args.cpu_seconds)
         cpu["cores_available"] = os.cpu_count()
     line = {

@@ -8,11 +8,11 @@ cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-.}"
 O=gpurun_out/base
 rm -rf $O && mkdir -p $O
 if [ "${SKIP_BENCH:-0}" != 1 ]; then
-    timeout -k 10 300 python3 bench.py ${BENCH_FULL_ARGS:-} > $O/bench.log 2>&1
+    timeout -k 10 300 python3 bench.py --full ${BENCH_FULL_ARGS:-} > $O/bench.log 2>&1
     rc=$?; echo "bench rc=$rc"; [ $rc -eq 0 ] || { tail -5 $O/bench.log; exit $rc; }
     grep '^{' $O/bench.log | tail -1 > $O/bench.json
 fi
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv -- python3 bench.py --steps 40 --warmup 3 --no-cpu-baseline --no-c3 --no-end-to-end --sustain-seconds 0.3 --settle-seconds 0.5 --iso-launches 0 ${TRACE_ARGS:-} > $O/trace.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv -- python3 bench.py --full --steps 40 --warmup 3 --no-cpu-baseline --no-c3 --no-end-to-end --sustain-seconds 0.3 --settle-seconds 0.5 --iso-launches 0 ${TRACE_ARGS:-} > $O/trace.log 2>&1
 rc=$?; echo "trace rc=$rc"; [ $rc -eq 0 ] || { tail -5 $O/trace.log; exit $rc; }
 python3 tools/trace_chain.py $(find $O/trace -name '*kernel_trace.csv' | head -1) $O/c2_timeline.json > /dev/null
 echo "timeline rc=$?"
