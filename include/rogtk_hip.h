@@ -549,6 +549,67 @@ int rogtk_str_transform_host(int op, const rogtk_str_col* cols, int n_cols, int6
                              rogtk_str_result* out);
 void rogtk_str_result_free(rogtk_str_result* r);
 
+/* ====== fuzzy pattern match / replace (the reference's `fuzzy` namespace, fuzzy.hip) ======
+ * fuzzy_contains_native_expr / fuzzy_replace_native_expr / fuzzy_contains_expr /
+ * fuzzy_replace_expr (src/expressions.rs:983-1216) without a regex engine: the patterns
+ * the reference generates from a literal target are a closed grammar, compiled here into
+ * a PROGRAM: an ordered list of alternatives, each a sequence of atoms
+ *     LIT(byte)  one literal byte
+ *     ANY        one code point that is not '\n'            (regex `.`)
+ *     OPT        zero or one such code point, greedy        (regex `.?` / `.{0,1}`)
+ * Matching rule (leftmost-first, as the regex crate and Python's re): the match of a row
+ * starts at the smallest offset b on a UTF-8 code-point boundary at which some alternative
+ * matches; among those the first in program order wins; OPT first consumes one code point
+ * and falls back to none only if the rest then fails. Null in -> null out; rows are valid
+ * UTF-8.
+ *
+ * Supported domain (anything else: ROGTK_E_UNSUPPORTED with the offending part named,
+ * never a wrong answer): native targets of 1..100 ASCII letters / digits; wildcard one of
+ * ".{0,1}", ".?", "."; pre-generated patterns that are '|'-separated sequences of ASCII
+ * letters / digits, ".", ".?" and ".{0,1}" (literal = 1: any non-empty bytes, one
+ * alternative of LITs); at most one OPT per alternative and no alternative that can match
+ * the empty string; a replacement of a non-literal program holds no '$' (the regex crate
+ * expands "$name"). A later alternative equal to an earlier one is dropped. */
+typedef struct rogtk_fuzzy_program rogtk_fuzzy_program;
+
+/* generate_fuzzy_pattern (:983-1013): the target (include_original), then the target with
+ * position 0, 1, .. replaced by the wildcard, then the target with its last character
+ * replaced by '.'; the variants only when target_len <= max_length. wildcard NULL: ".{0,1}". */
+int rogtk_fuzzy_compile_native(const uint8_t* target, int64_t target_len, const char* wildcard,
+                               int include_original, int64_t max_length, rogtk_fuzzy_program** out);
+/* a pre-generated pattern (fuzzy_contains_expr / fuzzy_replace_expr, :1104-1162) */
+int rogtk_fuzzy_compile_pattern(const uint8_t* pattern, int64_t pattern_len, int literal,
+                                rogtk_fuzzy_program** out);
+/* The replacement of the replace calls (copied). Not while a call that uses the program is
+ * in flight on a device. */
+int rogtk_fuzzy_set_replacement(rogtk_fuzzy_program* p, const uint8_t* replacement, int64_t len);
+void rogtk_fuzzy_free(rogtk_fuzzy_program* p);
+/* Canonical text of a program: the alternatives joined by '|', a LIT as its byte, ANY as
+ * '.', OPT as '?'. *out_len = bytes needed (ROGTK_E_OVERFLOW when > cap). No GPU needed. */
+int rogtk_fuzzy_describe(const rogtk_fuzzy_program* p, char* out, int64_t cap, int64_t* out_len);
+
+/* Level 1 (one device column, enqueue-only on `stream`; the first call of a program on a
+ * device also allocates and uploads the program there). contains: bit r of out_bits[r / 64]
+ * = row r matches, of out_valid_bits = row r is not null; (n + 63) / 64 words each.
+ * replace_measure / replace_fill: as rogtk_str_measure / rogtk_str_fill (temp:
+ * rogtk_str_temp_bytes(n) bytes); replace_all = 0 substitutes the first match only. The
+ * fill pass finds the matches again (nothing but the offsets is carried between the
+ * passes). col->n rows; a column with n = 0 is fine. */
+int rogtk_fuzzy_contains(rogtk_fuzzy_program* p, const rogtk_str_col* col, uint64_t* out_bits,
+                         uint64_t* out_valid_bits, void* stream);
+int rogtk_fuzzy_replace_measure(rogtk_fuzzy_program* p, const rogtk_str_col* col, int replace_all,
+                                int64_t* out_offsets, uint64_t* out_valid_bits, void* temp, int64_t temp_bytes,
+                                void* stream);
+int rogtk_fuzzy_replace_fill(rogtk_fuzzy_program* p, const rogtk_str_col* col, int replace_all,
+                             const int64_t* offsets, uint8_t* out_values, void* stream);
+
+/* Level 2 (one host column). contains: out_bits / out_valid_bits (nullable) are host
+ * buffers of (n + 63) / 64 words. replace: result as rogtk_str_transform_host. */
+int rogtk_fuzzy_contains_host(rogtk_fuzzy_program* p, const rogtk_str_col* col, uint64_t* out_bits,
+                              uint64_t* out_valid_bits);
+int rogtk_fuzzy_replace_host(rogtk_fuzzy_program* p, const rogtk_str_col* col, int replace_all,
+                             rogtk_str_result* out);
+
 /* ============================== profiling ================================ */
 /* When enabled, every kernel launch is bracketed by HIP events on its stream. */
 /* ======== multi-GPU exchange of read groups ========

@@ -33,6 +33,8 @@ from .assembly import (  # noqa: F401
 from .strings import (  # noqa: F401
     CigarNamespace,
     DnaNamespace,
+    FuzzyNamespace,
+    FuzzyProgram,
     extract_cigar_insertions,
     parse_cigar,
     phred_to_numeric,
@@ -62,5 +64,5 @@ __all__ = [
     "assemble_sequences_with_anchors", "sweep_assembly_params", "optimize_assembly", "assemble_groups",
     "assemble_column_groups", "iter_paired_fastqs",
     "parse_paired_fastqs", "DnaNamespace", "CigarNamespace", "reverse_complement", "parse_cigar",
-    "phred_to_numeric_str", "phred_to_numeric", "extract_cigar_insertions",
+    "phred_to_numeric_str", "phred_to_numeric", "extract_cigar_insertions", "FuzzyNamespace", "FuzzyProgram",
 ]

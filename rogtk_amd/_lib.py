@@ -199,6 +199,15 @@ SIGNATURES = {
     "rogtk_str_measure": [_i32, ctypes.POINTER(StrCol), _i32, _i64, _i64, _vp, _vp, _vp, _i64, _vp],
     "rogtk_str_fill": [_i32, ctypes.POINTER(StrCol), _i32, _i64, _i64, _vp, _vp, _vp],
     "rogtk_str_transform_host": [_i32, ctypes.POINTER(StrCol), _i32, _i64, _i64, ctypes.POINTER(StrResult)],
+    "rogtk_fuzzy_compile_native": [ctypes.c_char_p, _i64, ctypes.c_char_p, _i32, _i64, ctypes.POINTER(_vp)],
+    "rogtk_fuzzy_compile_pattern": [ctypes.c_char_p, _i64, _i32, ctypes.POINTER(_vp)],
+    "rogtk_fuzzy_set_replacement": [_vp, ctypes.c_char_p, _i64],
+    "rogtk_fuzzy_describe": [_vp, ctypes.c_char_p, _i64, _P_I64],
+    "rogtk_fuzzy_contains": [_vp, ctypes.POINTER(StrCol), _vp, _vp, _vp],
+    "rogtk_fuzzy_replace_measure": [_vp, ctypes.POINTER(StrCol), _i32, _vp, _vp, _vp, _i64, _vp],
+    "rogtk_fuzzy_replace_fill": [_vp, ctypes.POINTER(StrCol), _i32, _vp, _vp, _vp],
+    "rogtk_fuzzy_contains_host": [_vp, ctypes.POINTER(StrCol), _vp, _vp],
+    "rogtk_fuzzy_replace_host": [_vp, ctypes.POINTER(StrCol), _i32, ctypes.POINTER(StrResult)],
     "rogtk_profile_enable": [_i32],
     "rogtk_profile_select": [ctypes.c_char_p],
     "rogtk_profile_reset": [],
@@ -209,6 +218,7 @@ SIGNATURES = {
 # functions returning void
 VOID_SIGNATURES = {
     "rogtk_str_result_free": [ctypes.POINTER(StrResult)],
+    "rogtk_fuzzy_free": [_vp],
 }
 
 _lock = threading.Lock()

@@ -283,10 +283,11 @@ class Col:
         self.column = column
         self.umi = UmiNamespace(column)
         self.hamming = HammingExpr(column)
-        from .strings import CigarNamespace, DnaNamespace
+        from .strings import CigarNamespace, DnaNamespace, FuzzyNamespace
 
         self.dna = DnaNamespace(column)
         self.cigar = CigarNamespace(column)
+        self.fuzzy = FuzzyNamespace(column)
 
 
 def col(column: ColumnLike) -> Col:

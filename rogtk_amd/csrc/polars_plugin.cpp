@@ -996,6 +996,63 @@ void phred_list_expr(SeriesExport* in, size_t n_in, SeriesExport* out, int64_t b
     export_series(out, {"numeric_phred", "+L", {{"item", "C", {}}}}, std::move(chunks));
 }
 
+// -------------------------------------------------- fuzzy match / replace
+// fuzzy_contains_native_expr / fuzzy_replace_native_expr (native = true: the pattern is
+// generated from kwargs.target, expressions.rs:1164-1216) and fuzzy_contains_expr /
+// fuzzy_replace_expr (the caller's pre-generated pattern, :1104-1162).
+struct FuzzyProgramHolder {
+    rogtk_fuzzy_program* p = nullptr;
+    ~FuzzyProgramHolder() { rogtk_fuzzy_free(p); }
+};
+void fuzzy_expr(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out, bool native, bool replace) {
+    if (n_in < 1) fail("expected one input series");
+    FuzzyProgramHolder h;
+    bool all = true;  // Regex::replace_all / str::replace
+    if (native) {
+        const std::string target = kw.str("target");
+        std::string wildcard = ".{0,1}";
+        kw.opt_str("wildcard", &wildcard);
+        const bool include_original = kw.opt_bool("include_original", true);
+        const int64_t max_length = kw.opt_uint("max_length", 100);
+        if (replace) all = kw.opt_bool("replace_all", false);
+        check(rogtk_fuzzy_compile_native((const uint8_t*)target.data(), (int64_t)target.size(), wildcard.c_str(),
+                                         include_original, max_length, &h.p));
+    } else {
+        const std::string pattern = kw.str("pattern");
+        // (the reference deserialises contains' kwargs as FuzzyReplaceKwargs too, whose
+        // `replacement` its own Python never sends; contains does not ask for it here)
+        check(rogtk_fuzzy_compile_pattern((const uint8_t*)pattern.data(), (int64_t)pattern.size(),
+                                          kw.opt_bool("literal", false), &h.p));
+    }
+    if (replace) {
+        const std::string repl = kw.str("replacement");
+        check(rogtk_fuzzy_set_replacement(h.p, (const uint8_t*)repl.data(), (int64_t)repl.size()));
+    }
+    StrSeries s = str_series(in[0]);
+    FlatCol f = flatten_all(s);
+    const rogtk_str_col d = str_desc(f);
+    std::vector<Col> chunks;
+    if (replace) {
+        StrResultHolder r;
+        check(rogtk_fuzzy_replace_host(h.p, &d, all, &r.r));
+        chunks.push_back(view_col_result(r.r));
+        export_series(out, {s.name, "vu", {}}, std::move(chunks));
+        return;
+    }
+    const size_t words = (size_t)std::max<int64_t>((f.n + 63) / 64, 1);
+    std::vector<uint64_t> bits(words, 0);
+    check(rogtk_fuzzy_contains_host(h.p, &d, bits.data(), nullptr));
+    Col col;
+    col.length = f.n;
+    col.null_count = f.nulls;
+    col.bufs.push_back(f.nulls ? f.valid : std::vector<uint8_t>{});
+    std::vector<uint8_t> b(words * 8);
+    memcpy(b.data(), bits.data(), b.size());
+    col.bufs.push_back(std::move(b));
+    chunks.push_back(std::move(col));
+    export_series(out, {s.name, "b", {}}, std::move(chunks));
+}
+
 int64_t phred_base(const Kwargs& kw) {
     const int64_t b = kw.uint("base");  // Phred2NmKwargs.base: u8 (expressions.rs:493-496)
     if (b > 255) fail("could not parse kwargs: base does not fit in u8");
@@ -1180,5 +1237,19 @@ ROGTK_FIELD(phred_to_numeric_series_str, (FieldSpec{name, "vu", {}}))
 ROGTK_EXPR(phred_to_numeric_series,
            phred_list_expr(inputs, n_inputs, return_value, phred_base(parse_kwargs(kwargs_ptr, kwargs_len))))
 ROGTK_FIELD(phred_to_numeric_series, (FieldSpec{name, "+L", {{"item", "C", {}}}}))
+
+// fuzzy namespace (expressions.rs:1104-1216)
+ROGTK_EXPR(fuzzy_contains_native_expr,
+           fuzzy_expr(inputs, n_inputs, parse_kwargs(kwargs_ptr, kwargs_len), return_value, true, false))
+ROGTK_FIELD(fuzzy_contains_native_expr, (FieldSpec{name, "b", {}}))
+ROGTK_EXPR(fuzzy_replace_native_expr,
+           fuzzy_expr(inputs, n_inputs, parse_kwargs(kwargs_ptr, kwargs_len), return_value, true, true))
+ROGTK_FIELD(fuzzy_replace_native_expr, (FieldSpec{name, "vu", {}}))
+ROGTK_EXPR(fuzzy_contains_expr,
+           fuzzy_expr(inputs, n_inputs, parse_kwargs(kwargs_ptr, kwargs_len), return_value, false, false))
+ROGTK_FIELD(fuzzy_contains_expr, (FieldSpec{name, "b", {}}))
+ROGTK_EXPR(fuzzy_replace_expr,
+           fuzzy_expr(inputs, n_inputs, parse_kwargs(kwargs_ptr, kwargs_len), return_value, false, true))
+ROGTK_FIELD(fuzzy_replace_expr, (FieldSpec{name, "vu", {}}))
 
 }  // extern "C"

@@ -6,8 +6,8 @@ calls ``_polars_plugin_<function_name>`` in the first shared library of the pack
 directory. librogtk_hip.so is the only shared library in ``rogtk_amd/`` and exports
 those symbols (rogtk_amd/csrc/polars_plugin.cpp), so:
 
-* with polars installed, ``register_polars()`` registers the reference's ``umi`` and
-  ``hamming`` expression namespaces and the module-level functions below return
+* with polars installed, ``register_polars()`` registers the reference's ``umi``,
+  ``hamming`` and ``fuzzy`` expression namespaces and the module-level functions below return
   ``pl.Expr`` exactly as rogtk's do (same function names, kwargs and defaults);
 * without polars (this image), ``call_plugin`` drives the same symbols through the same
   calling convention polars uses: inputs exported over the Arrow C Data Interface into
@@ -38,6 +38,8 @@ EXPRESSIONS = (
     "reverse_complement_series", "parse_cigar_series", "cigar_aligned_ref_expr", "cigar_aligned_query_expr",
     "extract_cigar_insertions_expr", "enrich_allele_insertions_expr", "phred_to_numeric_series_str",
     "phred_to_numeric_series",
+    # fuzzy namespace (expressions.rs:1104-1216)
+    "fuzzy_contains_native_expr", "fuzzy_replace_native_expr", "fuzzy_contains_expr", "fuzzy_replace_expr",
 )
 
 
@@ -223,6 +225,32 @@ def register_polars():
             return reg("hamming_within_expr", self._expr, {"target": target, "max_distance": max_distance},
                        is_elementwise=True)
 
+    @pl.api.register_expr_namespace("fuzzy")
+    class FuzzyExpr:  # rogtk/__init__.py:351-410
+        def __init__(self, expr):
+            self._expr = expr
+
+        def replace(self, pattern: str, replacement: str, literal: bool = False):
+            return reg("fuzzy_replace_expr", self._expr,
+                       {"pattern": pattern, "replacement": replacement, "literal": literal}, is_elementwise=True)
+
+        def contains(self, pattern: str, literal: bool = False):
+            return reg("fuzzy_contains_expr", self._expr, {"pattern": pattern, "literal": literal},
+                       is_elementwise=True)
+
+        def match(self, target: str, wildcard: str = ".{0,1}", include_original: bool = True,
+                  max_length: int = 100):
+            return reg("fuzzy_contains_native_expr", self._expr,
+                       {"target": target, "wildcard": wildcard, "include_original": include_original,
+                        "max_length": max_length}, is_elementwise=True)
+
+        def replace_target(self, target: str, replacement: str, wildcard: str = ".{0,1}",
+                           include_original: bool = True, max_length: int = 100, replace_all: bool = False):
+            return reg("fuzzy_replace_native_expr", self._expr,
+                       {"target": target, "replacement": replacement, "wildcard": wildcard,
+                        "include_original": include_original, "max_length": max_length,
+                        "replace_all": replace_all}, is_elementwise=True)
+
     @pl.api.register_expr_namespace("umi")
     class UmiNamespace:  # rogtk/__init__.py:412-491
         def __init__(self, expr):
@@ -298,7 +326,7 @@ def register_polars():
                     "explore_k": explore_k, "prioritize_length": prioritize_length},
                    returns_scalar=True, is_elementwise=False)
 
-    return {"HammingExpr": HammingExpr, "UmiNamespace": UmiNamespace, "umi_complexity_scores": umi_complexity_scores,
+    return {"HammingExpr": HammingExpr, "FuzzyExpr": FuzzyExpr, "UmiNamespace": UmiNamespace, "umi_complexity_scores": umi_complexity_scores,
             "assemble_sequences": assemble_sequences,
             "assemble_sequences_with_anchors": assemble_sequences_with_anchors,
             "sweep_assembly_params": sweep_assembly_params, "optimize_assembly": optimize_assembly}

@@ -8,6 +8,8 @@ Mirrors the reference's Python surface (rogtk/__init__.py) on pyarrow columns:
     src/expressions.rs:598-630  phred_to_numeric_series (List[u8]; not registered in Python)
     rogtk/__init__.py:532-658   CigarNamespace.enrich_insertions / align_to_ref / align_to_query
     rogtk/__init__.py:661-696   extract_cigar_insertions(seq_col, cigar_col)
+    rogtk/__init__.py:351-410   FuzzyExpr.match / replace_target / contains / replace
+                                -> fuzzy_*_expr (rogtk_amd/csrc/fuzzy.hip, wave per row)
 
 Every call runs rogtk_str_transform_host (rogtk_amd/csrc/strings.hip): a measuring
 and a filling kernel over the rows, thread per row. There is no CPU path.
@@ -15,7 +17,7 @@ and a filling kernel over the rows, thread per row. There is no CPU path.
 from __future__ import annotations
 
 import ctypes
-from typing import List
+from typing import List, Optional
 
 import numpy as np
 import pyarrow as pa
@@ -60,8 +62,13 @@ def _transform(op: int, cols: List[ColumnLike], param: int = 0):
     keep: list = []
     descs = (_lib.StrCol * len(arrays))(*[_desc(a, keep) for a in arrays])
     res = _lib.StrResult()
+    _lib.check(_lib.hip().rogtk_str_transform_host(op, descs, len(arrays), n, int(param), ctypes.byref(res)))
+    return _take_result(res, n)
+
+
+def _take_result(res: _lib.StrResult, n: int):
+    """Copies of a rogtk_str_result's buffers; frees the result."""
     lib = _lib.hip()
-    _lib.check(lib.rogtk_str_transform_host(op, descs, len(arrays), n, int(param), ctypes.byref(res)))
     try:
         offs = np.ctypeslib.as_array(ctypes.cast(res.offsets, ctypes.POINTER(ctypes.c_int64)), (n + 1,)).copy()
         vals = np.ctypeslib.as_array(ctypes.cast(res.values, ctypes.POINTER(ctypes.c_uint8)),
@@ -140,3 +147,111 @@ class CigarNamespace:
     def align_to_query(self, query_col: ColumnLike, cigar_col: ColumnLike):
         """cigar_aligned_query_expr (expressions.rs:396-444)."""
         return _string_array(*_transform(ALIGNED_QUERY, [self._c, query_col, cigar_col]))
+
+
+# ------------------------------------------------------------------ fuzzy
+class FuzzyProgram:
+    """A compiled fuzzy pattern (rogtk_fuzzy_program, include/rogtk_hip.h): an ordered list of
+    alternatives over literal bytes, "." and an optional ".". Compiling and ``describe`` need
+    no GPU; a pattern outside the supported grammar raises RogtkError (ROGTK_E_UNSUPPORTED)."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @staticmethod
+    def _bytes(s) -> bytes:
+        return s.encode("utf-8") if isinstance(s, str) else bytes(s)
+
+    @classmethod
+    def native(cls, target, wildcard: Optional[str] = None, include_original: Optional[bool] = None,
+               max_length: Optional[int] = None) -> "FuzzyProgram":
+        """generate_fuzzy_pattern (expressions.rs:983-1013); None = the reference's default."""
+        t = cls._bytes(target)
+        h = ctypes.c_void_p()
+        _lib.call("rogtk_fuzzy_compile_native", t, len(t), cls._bytes(".{0,1}" if wildcard is None else wildcard),
+                  1 if include_original is None else int(bool(include_original)),
+                  100 if max_length is None else int(max_length), ctypes.byref(h))
+        return cls(h)
+
+    @classmethod
+    def pattern(cls, pattern, literal: Optional[bool] = None) -> "FuzzyProgram":
+        p = cls._bytes(pattern)
+        h = ctypes.c_void_p()
+        _lib.call("rogtk_fuzzy_compile_pattern", p, len(p), int(bool(literal)), ctypes.byref(h))
+        return cls(h)
+
+    @property
+    def handle(self) -> ctypes.c_void_p:
+        return self._h
+
+    def set_replacement(self, replacement) -> "FuzzyProgram":
+        r = self._bytes(replacement)
+        _lib.call("rogtk_fuzzy_set_replacement", self._h, r, len(r))
+        return self
+
+    def describe(self) -> str:
+        """The alternatives joined by '|': literal bytes, '.' (any), '?' (optional any)."""
+        need = ctypes.c_int64(0)
+        rc = _lib.hip().rogtk_fuzzy_describe(self._h, None, 0, ctypes.byref(need))
+        if rc not in (_lib.ROGTK_OK, _lib.ROGTK_E_OVERFLOW):
+            _lib.check(rc)
+        buf = ctypes.create_string_buffer(max(int(need.value), 1))
+        _lib.call("rogtk_fuzzy_describe", self._h, buf, int(need.value), ctypes.byref(need))
+        return buf.raw[: need.value].decode("utf-8", "replace")
+
+    def contains(self, column: ColumnLike) -> pa.Array:
+        a = _single(column)
+        n = len(a)
+        keep: list = []
+        d = _desc(a, keep)
+        bits = np.zeros(max((n + 63) // 64, 1), dtype=np.uint64)
+        vbits = np.zeros_like(bits)
+        _lib.call("rogtk_fuzzy_contains_host", self._h, ctypes.byref(d), bits.ctypes.data, vbits.ctypes.data)
+        nulls = a.null_count
+        return pa.Array.from_buffers(pa.bool_(), n, [pa.py_buffer(vbits) if nulls else None, pa.py_buffer(bits)],
+                                     null_count=nulls)
+
+    def replace(self, column: ColumnLike, replace_all: bool) -> pa.Array:
+        a = _single(column)
+        keep: list = []
+        d = _desc(a, keep)
+        res = _lib.StrResult()
+        _lib.call("rogtk_fuzzy_replace_host", self._h, ctypes.byref(d), int(bool(replace_all)), ctypes.byref(res))
+        return _string_array(*_take_result(res, len(a)))
+
+    def close(self) -> None:
+        if self._h is not None and self._h.value:
+            _lib.hip().rogtk_fuzzy_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FuzzyNamespace:
+    """rogtk/__init__.py:351-410 (`pl.col(..).fuzzy.*`). ``match`` / ``contains`` return a
+    BooleanArray, the replace methods a large_string array; null in, null out."""
+
+    def __init__(self, column: ColumnLike):
+        self._c = column
+
+    def replace(self, pattern: str, replacement: str, literal: bool = False):
+        """fuzzy_replace_expr (expressions.rs:1104-1129): every match (Regex::replace_all / str::replace)."""
+        return FuzzyProgram.pattern(pattern, literal).set_replacement(replacement).replace(self._c, True)
+
+    def contains(self, pattern: str, literal: bool = False):
+        """fuzzy_contains_expr (expressions.rs:1131-1162)."""
+        return FuzzyProgram.pattern(pattern, literal).contains(self._c)
+
+    def match(self, target: str, wildcard: str = ".{0,1}", include_original: bool = True, max_length: int = 100):
+        """fuzzy_contains_native_expr (expressions.rs:1164-1188)."""
+        return FuzzyProgram.native(target, wildcard, include_original, max_length).contains(self._c)
+
+    def replace_target(self, target: str, replacement: str, wildcard: str = ".{0,1}", include_original: bool = True,
+                       max_length: int = 100, replace_all: bool = False):
+        """fuzzy_replace_native_expr (expressions.rs:1190-1216)."""
+        prog = FuzzyProgram.native(target, wildcard, include_original, max_length).set_replacement(replacement)
+        return prog.replace(self._c, bool(replace_all))
