@@ -610,6 +610,82 @@ int rogtk_fuzzy_contains_host(rogtk_fuzzy_program* p, const rogtk_str_col* col, 
 int rogtk_fuzzy_replace_host(rogtk_fuzzy_program* p, const rogtk_str_col* col, int replace_all,
                              rogtk_str_result* out);
 
+/* ====== UMI correction: cluster representatives, sizes, corrected UMIs (correct.hip) ======
+ * The step after H3 (spec: DESIGN.md §4b; the reference has none and groups on the host,
+ * rogtk/__init__.py:206-214). Inputs: a string column and the cluster id of every row (dense
+ * 0..n_clusters-1, 0xFFFFFFFF for a null row; from the H3 entry points with the same umi_len
+ * and max_distance, or the caller's own). Per cluster c:
+ *   n_reads[c]        non-null rows with id c
+ *   n_distinct[c]     distinct byte strings among them
+ *   representative[c] the distinct string with the most rows; ties: a regular string (byte
+ *                     length umi_len, only ACGT) before an irregular one, then the
+ *                     byte-lexicographically smallest (for regular strings: the smallest code)
+ * and per row corrected[i] = representative[id[i]] (null in -> null out). */
+
+/* Level 1, packed SoA (umi_len 1..16; regular rows only: the other rows are not counted and
+ * get corrected code 0xFFFFFFFF). Enqueue-only. cluster_id as written by rogtk_cluster_assign:
+ * equal codes carry equal ids (rows whose id is >= n_clusters are skipped). rep_code[c] is
+ * 0xFFFFFFFF and n_reads[c] 0 for an id without regular rows. temp: device scratch of
+ * rogtk_cluster_summary_temp_bytes() bytes. regular_bits == NULL: every row is regular. */
+int rogtk_cluster_summary_temp_bytes(int64_t n, int umi_len, int64_t n_clusters, int64_t* bytes);
+int rogtk_cluster_summary_packed(const uint32_t* codes, const uint64_t* regular_bits, int64_t n, int umi_len,
+                                 const uint32_t* cluster_id, int64_t n_clusters, uint32_t* rep_code /* [n_clusters] */,
+                                 uint32_t* n_reads /* [n_clusters] */, uint32_t* n_distinct /* [n_clusters] */,
+                                 void* temp, int64_t temp_bytes, void* stream);
+/* corrected_codes[i] = rep_code[cluster_id[i]] for regular rows with an id < n_clusters,
+ * 0xFFFFFFFF for the others. */
+int rogtk_cluster_correct_packed(const uint32_t* cluster_id, const uint64_t* regular_bits, int64_t n,
+                                 const uint32_t* rep_code, int64_t n_clusters, uint32_t* corrected_codes /* [n] */,
+                                 void* stream);
+/* How rogtk_cluster_summary_packed counts rows per distinct code, process-wide (A/B knob,
+ * identical tables): 0 = radix sort of (code, id) + run lengths (default), 1 = a u32 count
+ * table over the 4^umi_len code space with one atomic per row (umi_len <= 12, else 0). */
+int rogtk_cluster_summary_set_method(int method);
+
+/* Level 1, device column (layout as rogtk_umi_cluster_dev: int64 offsets from 0, values,
+ * optional validity bitmap at bit offset 0), any strings, caller-supplied ids. Device outputs:
+ * n_reads / n_distinct [n_clusters], rep_rows[n_clusters] (a row holding the representative;
+ * -1 for an id without rows: empty representative) and, in measure / fill form,
+ * rep_offsets[n_clusters + 1]; *rep_values_len (host) = bytes of all representatives, which
+ * sizes rep_values for rogtk_cluster_representatives_fill. umi_len >= 1 decides "regular".
+ * ROGTK_E_INVALID when a non-null row's id is >= n_clusters. Synchronises `stream`. */
+int rogtk_cluster_summary_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
+                              int umi_len, const uint32_t* cluster_id, int64_t n_clusters, uint32_t* n_reads,
+                              uint32_t* n_distinct, int64_t* rep_rows, int64_t* rep_offsets, int64_t* rep_values_len,
+                              void* stream);
+int rogtk_cluster_representatives_fill(const int64_t* offsets, const uint8_t* values, const int64_t* rep_rows,
+                                       int64_t n_clusters, const int64_t* rep_offsets, uint8_t* rep_values,
+                                       void* stream);
+/* rogtk_umi_cluster_dev, the summary and the correction in one call: cluster_id[n] (device),
+ * *n_clusters (host) and corrected_values, the corrected column's bytes under the INPUT's
+ * offsets (every member of an H3 cluster has its representative's byte length); bytes under
+ * null rows are left as they were. Synchronises `stream`. */
+int rogtk_umi_correct_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
+                          int umi_len, int max_distance, uint32_t* cluster_id, int64_t* n_clusters,
+                          uint8_t* corrected_values, void* stream);
+
+/* Level 2, host column. The library allocates the results (string results as
+ * rogtk_str_transform_host, freed with rogtk_str_result_free; the per-cluster counts as
+ * rogtk_u32_result, freed with rogtk_u32_result_free), so the caller never guesses n_clusters.
+ * umi_len <= 0: the length of the first non-null row. Argument errors are reported before any
+ * device work. */
+typedef struct rogtk_u32_result {
+    int64_t n;
+    uint32_t* data;
+} rogtk_u32_result;
+void rogtk_u32_result_free(rogtk_u32_result* r);
+/* H3 (as rogtk_umi_cluster_host: cluster_id[n], *n_clusters, *resolved_umi_len) + summary +
+ * correction. corrected: n rows with the input's nulls; representatives / n_reads /
+ * n_distinct: *n_clusters entries in cluster-id order. */
+int rogtk_umi_correct_host(const rogtk_str_col* col, int umi_len, int max_distance, uint32_t* cluster_id,
+                           rogtk_str_result* corrected, rogtk_str_result* representatives, rogtk_u32_result* n_reads,
+                           rogtk_u32_result* n_distinct, int64_t* n_clusters, int* resolved_umi_len);
+/* The summary for caller-supplied ids (members of a cluster may differ in length).
+ * ROGTK_E_INVALID when a non-null row's id is >= n_clusters. */
+int rogtk_cluster_summary_host(const rogtk_str_col* col, int umi_len, const uint32_t* cluster_id, int64_t n_clusters,
+                               rogtk_str_result* representatives, rogtk_u32_result* n_reads,
+                               rogtk_u32_result* n_distinct);
+
 /* ============================== profiling ================================ */
 /* When enabled, every kernel launch is bracketed by HIP events on its stream. */
 /* ======== multi-GPU exchange of read groups ========
@@ -740,7 +816,8 @@ int rogtk_copy(void* dst, const void* src, int64_t bytes, void* stream);
  * dust_score}_expr (expressions.rs:1234-1410), hamming_{distance,within}_expr
  * (:1048-1101), assemble_sequences_expr (:695), assemble_sequences_with_anchors_expr
  * (:770), sweep_assembly_params_expr (:880), optimize_assembly_expr
- * (fracture_opt.rs:283). The structs are the Arrow C Data Interface and polars-ffi
+ * (fracture_opt.rs:283), and umi_correct_expr (no reference counterpart: the corrected UMI
+ * of every row, kwargs umi_len / max_distance, the whole series one batch). The structs are the Arrow C Data Interface and polars-ffi
  * version_0's SeriesExport {ArrowSchema* field; ArrowArray** arrays; size_t len;
  * void (*release)(SeriesExport*); void* private_data;}; see INTEGRATION.md.
  * Diagnostics: the kwargs pickle as the plugin parses it, "key=value" lines. */

@@ -9,6 +9,7 @@ Drop-in surface (mirrors rogtk/__init__.py's `umi` / `hamming` namespaces):
     rg.col(umis).hamming.within("ACGTACGTACGT", max_distance=1)
     rg.umi_complexity_scores(umis)
     rg.umi_cluster(umis, max_distance=1)         # H3 (caller-side group_by('umi'))
+    rg.umi_correct(umis, max_distance=1)         # representatives, sizes, corrected UMIs
     rg.kmer_spectrum(reads, k=17, min_coverage=20, group_offsets=...)  # H4 (fracture.rs)
     rg.assemble_sequences(group_reads, k=13, min_coverage=1, method="compression")  # H5
     rg.assemble_column_groups(offsets, values, cluster_ids, k=10, min_coverage=5)  # H5, all groups
@@ -41,6 +42,7 @@ from .strings import (  # noqa: F401
     phred_to_numeric_str,
     reverse_complement,
 )
+from .correct import UmiCorrection, umi_cluster_summary, umi_correct  # noqa: F401
 from .api import (  # noqa: F401
     FIELDS,
     KMER_STATS,
@@ -65,4 +67,5 @@ __all__ = [
     "assemble_column_groups", "iter_paired_fastqs",
     "parse_paired_fastqs", "DnaNamespace", "CigarNamespace", "reverse_complement", "parse_cigar",
     "phred_to_numeric_str", "phred_to_numeric", "extract_cigar_insertions", "FuzzyNamespace", "FuzzyProgram",
+    "umi_correct", "umi_cluster_summary", "UmiCorrection",
 ]

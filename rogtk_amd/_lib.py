@@ -85,6 +85,12 @@ class StrResult(ctypes.Structure):
     ]
 
 
+class U32Result(ctypes.Structure):
+    """rogtk_u32_result (include/rogtk_hip.h): library-allocated uint32 array."""
+
+    _fields_ = [("n", ctypes.c_int64), ("data", ctypes.c_void_p)]
+
+
 _vp, _i64, _i32, _u32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_uint32
 _P_SCORES = ctypes.POINTER(UmiScores)
 _P_I64 = ctypes.POINTER(ctypes.c_int64)
@@ -208,6 +214,18 @@ SIGNATURES = {
     "rogtk_fuzzy_replace_fill": [_vp, ctypes.POINTER(StrCol), _i32, _vp, _vp, _vp],
     "rogtk_fuzzy_contains_host": [_vp, ctypes.POINTER(StrCol), _vp, _vp],
     "rogtk_fuzzy_replace_host": [_vp, ctypes.POINTER(StrCol), _i32, ctypes.POINTER(StrResult)],
+    "rogtk_cluster_summary_temp_bytes": [_i64, _i32, _i64, _P_I64],
+    "rogtk_cluster_summary_packed": [_vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp],
+    "rogtk_cluster_correct_packed": [_vp, _vp, _i64, _vp, _i64, _vp, _vp],
+    "rogtk_cluster_summary_set_method": [_i32],
+    "rogtk_cluster_summary_dev": [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _P_I64, _vp],
+    "rogtk_cluster_representatives_fill": [_vp, _vp, _vp, _i64, _vp, _vp, _vp],
+    "rogtk_umi_correct_dev": [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _P_I64, _vp, _vp],
+    "rogtk_umi_correct_host": [ctypes.POINTER(StrCol), _i32, _i32, _vp, ctypes.POINTER(StrResult),
+                               ctypes.POINTER(StrResult), ctypes.POINTER(U32Result), ctypes.POINTER(U32Result),
+                               _P_I64, _P_I32],
+    "rogtk_cluster_summary_host": [ctypes.POINTER(StrCol), _i32, _vp, _i64, ctypes.POINTER(StrResult),
+                                   ctypes.POINTER(U32Result), ctypes.POINTER(U32Result)],
     "rogtk_profile_enable": [_i32],
     "rogtk_profile_select": [ctypes.c_char_p],
     "rogtk_profile_reset": [],
@@ -219,6 +237,7 @@ SIGNATURES = {
 VOID_SIGNATURES = {
     "rogtk_str_result_free": [ctypes.POINTER(StrResult)],
     "rogtk_fuzzy_free": [_vp],
+    "rogtk_u32_result_free": [ctypes.POINTER(U32Result)],
 }
 
 _lock = threading.Lock()

@@ -13,6 +13,7 @@ reference                                          rogtk_amd
 ``pl.col(c).hamming.distance(target)`` (:331)      ``col(c).hamming.distance(target)``
 ``pl.col(c).hamming.within(target, 1)`` (:341)     ``col(c).hamming.within(target, 1)``
 ``df.group_by('umi')`` (caller, :206-214)          ``umi_cluster(c, max_distance=0|1)``
+(no counterpart: group_by + mode on the host)      ``umi_correct(c)``, ``col(c).umi.correct()``
 k-mer front end of ``assemble_sequences*`` per     ``kmer_spectrum(c, k, min_coverage,
 group (fracture.rs:105-256, debruijn                auto_k, group_offsets)``
 filter_kmers)
@@ -261,6 +262,13 @@ class UmiNamespace:
     def cluster(self, umi_len: int = 0, max_distance: int = 1):
         """Extension (no reference counterpart): H3 cluster ids."""
         return umi_cluster(self._c, umi_len, max_distance)[0]
+
+    def correct(self, umi_len: int = 0, max_distance: int = 1):
+        """Extension (no reference counterpart): every row's UMI replaced by the
+        representative of its H3 cluster."""
+        from .correct import umi_correct
+
+        return umi_correct(self._c, umi_len, max_distance).corrected
 
 
 class HammingExpr:

@@ -1105,18 +1105,12 @@ int rogtk_umi_cluster_host(const void* offsets, int offset_width, const uint8_t*
     return c->d2h(cluster_id, did, (size_t)n * 4);
 }
 
-int rogtk_umi_cluster_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
-                          int umi_len, int max_distance, uint32_t* cluster_id, int64_t* n_clusters, void* stream) {
-    ROGTK_REQUIRE(n >= 0 && (n == 0 || (offsets && values && cluster_id)), ROGTK_E_INVALID,
-                  "umi_cluster_dev: NULL argument");
-    ROGTK_REQUIRE(umi_len >= 1, ROGTK_E_INVALID, "umi_cluster_dev: umi_len must be >= 1");
-    ROGTK_REQUIRE(max_distance == 0 || max_distance == 1, ROGTK_E_UNSUPPORTED,
-                  "max_distance %d: only 0 and 1 are supported", max_distance);
-    if (n_clusters) *n_clusters = 0;
-    if (n == 0) return ROGTK_OK;
-    hipStream_t s = as_stream(stream);
-    HostCtx* c;
-    if (int rc = host_ctx(&c)) return rc;
+namespace {
+
+// rogtk_umi_cluster_dev on the context's buffers; *max_len = the column's longest row.
+static int cluster_dev(HostCtx* c, const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
+                int umi_len, int max_distance, uint32_t* cluster_id, int64_t* n_clusters, int64_t* max_len,
+                hipStream_t s) {
     const int64_t words = (n + 63) / 64;
     if (c->codes.ensure((size_t)std::max<int64_t>(n, 4) * 4) != ROGTK_OK ||
         c->regbits.ensure((size_t)std::max<int64_t>(words, 1) * 8) != ROGTK_OK ||
@@ -1132,8 +1126,336 @@ int rogtk_umi_cluster_dev(const int64_t* offsets, const uint8_t* values, const u
     int64_t hv[2];
     ROGTK_HIP_CHECK(hipMemcpyAsync(hv, c->nirr.p, 16, hipMemcpyDeviceToHost, s));
     ROGTK_HIP_CHECK(hipStreamSynchronize(s));
+    if (max_len) *max_len = hv[1];
     return cluster_staged(c, offsets, 8, values, validity, 0, n, umi_len, hv[0], hv[1], max_distance, cluster_id,
                           n_clusters, s);
+}
+
+}  // namespace
+
+int rogtk_umi_cluster_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
+                          int umi_len, int max_distance, uint32_t* cluster_id, int64_t* n_clusters, void* stream) {
+    ROGTK_REQUIRE(n >= 0 && (n == 0 || (offsets && values && cluster_id)), ROGTK_E_INVALID,
+                  "umi_cluster_dev: NULL argument");
+    ROGTK_REQUIRE(umi_len >= 1, ROGTK_E_INVALID, "umi_cluster_dev: umi_len must be >= 1");
+    ROGTK_REQUIRE(max_distance == 0 || max_distance == 1, ROGTK_E_UNSUPPORTED,
+                  "max_distance %d: only 0 and 1 are supported", max_distance);
+    if (n_clusters) *n_clusters = 0;
+    if (n == 0) return ROGTK_OK;
+    HostCtx* c;
+    if (int rc = host_ctx(&c)) return rc;
+    return cluster_dev(c, offsets, values, validity, n, umi_len, max_distance, cluster_id, n_clusters, nullptr,
+                       as_stream(stream));
+}
+
+// ------------------------------------------------- UMI correction (correct.hip)
+int rogtk_cluster_summary_set_method(int method) { return cluster_summary_set_method(method); }
+
+int rogtk_cluster_summary_temp_bytes(int64_t n, int umi_len, int64_t n_clusters, int64_t* bytes) {
+    ROGTK_REQUIRE(bytes, ROGTK_E_INVALID, "cluster_summary_temp_bytes: NULL bytes");
+    ROGTK_REQUIRE(umi_len >= 1 && umi_len <= kMaxPackedLen, ROGTK_E_UNSUPPORTED,
+                  "packed cluster summary: umi_len %d outside 1..%d", umi_len, kMaxPackedLen);
+    ROGTK_REQUIRE(n >= 0 && n < (1ll << 31), ROGTK_E_UNSUPPORTED, "packed cluster summary: n %lld outside 0..2^31-1",
+                  (long long)n);
+    ROGTK_REQUIRE(n_clusters >= 0 && n_clusters < (1ll << 32) - 1, ROGTK_E_INVALID,
+                  "packed cluster summary: bad n_clusters %lld", (long long)n_clusters);
+    return cluster_summary_packed_temp(n, umi_len, n_clusters, bytes);
+}
+
+int rogtk_cluster_summary_packed(const uint32_t* codes, const uint64_t* regular_bits, int64_t n, int umi_len,
+                                 const uint32_t* cluster_id, int64_t n_clusters, uint32_t* rep_code, uint32_t* n_reads,
+                                 uint32_t* n_distinct, void* temp, int64_t temp_bytes, void* stream) {
+    ROGTK_REQUIRE(umi_len >= 1 && umi_len <= kMaxPackedLen, ROGTK_E_UNSUPPORTED,
+                  "packed cluster summary: umi_len %d outside 1..%d", umi_len, kMaxPackedLen);
+    ROGTK_REQUIRE(n >= 0 && n < (1ll << 31), ROGTK_E_UNSUPPORTED, "packed cluster summary: n %lld outside 0..2^31-1",
+                  (long long)n);
+    ROGTK_REQUIRE(n_clusters >= 0 && n_clusters < (1ll << 32) - 1, ROGTK_E_INVALID,
+                  "packed cluster summary: bad n_clusters %lld", (long long)n_clusters);
+    ROGTK_REQUIRE(n == 0 || (codes && cluster_id), ROGTK_E_INVALID, "packed cluster summary: NULL codes / cluster_id");
+    ROGTK_REQUIRE(n_clusters == 0 || (rep_code && n_reads && n_distinct), ROGTK_E_INVALID,
+                  "packed cluster summary: NULL output table");
+    ROGTK_REQUIRE(temp, ROGTK_E_INVALID, "packed cluster summary: NULL temp");
+    return launch_cluster_summary_packed(codes, regular_bits, n, umi_len, cluster_id, n_clusters, rep_code, n_reads,
+                                         n_distinct, temp, temp_bytes, as_stream(stream));
+}
+
+int rogtk_cluster_correct_packed(const uint32_t* cluster_id, const uint64_t* regular_bits, int64_t n,
+                                 const uint32_t* rep_code, int64_t n_clusters, uint32_t* corrected_codes,
+                                 void* stream) {
+    ROGTK_REQUIRE(n >= 0 && n_clusters >= 0, ROGTK_E_INVALID, "packed correct: negative size");
+    ROGTK_REQUIRE(n == 0 || (cluster_id && corrected_codes && (rep_code || n_clusters == 0)), ROGTK_E_INVALID,
+                  "packed correct: NULL argument");
+    return launch_cluster_correct_packed(cluster_id, regular_bits, n, rep_code, n_clusters, corrected_codes,
+                                         as_stream(stream));
+}
+
+namespace {
+
+static void u32_result_reset(rogtk_u32_result* r) {
+    if (r) *r = rogtk_u32_result{0, nullptr};
+}
+
+static int empty_str_result(int64_t n, rogtk_str_result* out) {
+    const int64_t words = std::max<int64_t>((n + 63) / 64, 1);
+    out->n = n;
+    out->offsets = (int64_t*)calloc((size_t)n + 1, 8);
+    out->values = (uint8_t*)calloc(1, 1);
+    out->validity = (uint8_t*)calloc((size_t)words, 8);
+    out->values_len = 0;
+    out->null_count = 0;
+    ROGTK_REQUIRE(out->offsets && out->values && out->validity, ROGTK_E_INVALID, "out of host memory");
+    return ROGTK_OK;
+}
+
+// The three per-cluster tables of a column on the context's device buffers (ids in did):
+// counts to the host results, representatives measured, filled and copied into `reps`.
+static int summary_to_host(HostCtx* c, const void* d_offsets, int ow, const uint8_t* d_values, const uint8_t* d_validity,
+                    int64_t voff, int64_t n, int L, const uint32_t* did, int64_t nclu, int64_t max_len,
+                    rogtk_str_result* reps, rogtk_u32_result* n_reads, rogtk_u32_result* n_distinct) {
+    hipStream_t s = c->stream;
+    const int64_t nc1 = std::max<int64_t>(nclu, 1);
+    int64_t tb = 0;
+    if (int rc = representatives_temp(nclu, &tb)) return rc;
+    if (c->out[1].ensure((size_t)nc1 * 4) || c->out[2].ensure((size_t)nc1 * 4) || c->out[3].ensure((size_t)nc1 * 8) ||
+        c->out[4].ensure((size_t)(nclu + 1) * 8) || c->out[5].ensure((size_t)tb))
+        return ROGTK_E_HIP;
+    int64_t* rep_row = c->out[3].as<int64_t>();
+    if (int rc = cluster_summary_general(d_offsets, ow, d_values, d_validity, voff, n, L, did, nclu, max_len,
+                                         c->out[1].as<uint32_t>(), c->out[2].as<uint32_t>(), rep_row, s))
+        return rc;
+    if (int rc = representatives_measure(d_offsets, ow, rep_row, nclu, c->out[4].as<int64_t>(), c->out[5].p, tb, s))
+        return rc;
+    if (int rc = empty_str_result(nclu, reps)) return rc;
+    for (rogtk_u32_result* r : {n_reads, n_distinct}) {
+        r->n = nclu;
+        r->data = (uint32_t*)calloc((size_t)nc1, 4);
+        ROGTK_REQUIRE(r->data, ROGTK_E_INVALID, "out of host memory");
+    }
+    if (nclu > 0) {
+        if (int rc = c->d2h(n_reads->data, c->out[1].p, (size_t)nclu * 4)) return rc;
+        if (int rc = c->d2h(n_distinct->data, c->out[2].p, (size_t)nclu * 4)) return rc;
+    }
+    if (int rc = c->d2h(reps->offsets, c->out[4].p, (size_t)(nclu + 1) * 8)) return rc;
+    const int64_t total = reps->offsets[nclu];
+    for (int64_t k = 0; k < nclu; ++k) reps->validity[k >> 3] |= (uint8_t)(1u << (k & 7));
+    if (total > 0) {
+        free(reps->values);
+        reps->values = (uint8_t*)malloc((size_t)total);
+        ROGTK_REQUIRE(reps->values, ROGTK_E_INVALID, "out of host memory for %lld output bytes", (long long)total);
+        reps->values_len = total;
+        if (c->out[6].ensure((size_t)total)) return ROGTK_E_HIP;
+        if (int rc = representatives_fill(d_offsets, ow, d_values, rep_row, nclu, c->out[4].as<int64_t>(),
+                                          c->out[6].as<uint8_t>(), s))
+            return rc;
+        if (int rc = c->d2h(reps->values, c->out[6].p, (size_t)total)) return rc;
+    }
+    return ROGTK_OK;
+}
+
+static int check_correct_outputs(const rogtk_str_col* col, rogtk_str_result* reps, rogtk_u32_result* n_reads,
+                          rogtk_u32_result* n_distinct) {
+    ROGTK_REQUIRE(col, ROGTK_E_INVALID, "NULL column");
+    ROGTK_REQUIRE(reps && n_reads && n_distinct, ROGTK_E_INVALID,
+                  "NULL output (representatives, n_reads and n_distinct are required)");
+    *reps = rogtk_str_result{};
+    u32_result_reset(n_reads);
+    u32_result_reset(n_distinct);
+    return ROGTK_OK;
+}
+
+}  // namespace
+
+int rogtk_cluster_summary_host(const rogtk_str_col* col, int umi_len, const uint32_t* cluster_id, int64_t n_clusters,
+                               rogtk_str_result* representatives, rogtk_u32_result* n_reads,
+                               rogtk_u32_result* n_distinct) {
+    if (int rc = check_correct_outputs(col, representatives, n_reads, n_distinct)) return rc;
+    HostCol h{col->offsets, col->offset_width, col->values, col->values_len, col->validity, col->validity_offset,
+              col->n};
+    if (int rc = check_host_col(h)) return rc;
+    const int64_t n = h.n;
+    ROGTK_REQUIRE(n < (1ll << 31), ROGTK_E_UNSUPPORTED, "cluster summary: at most 2^31 - 1 rows");
+    ROGTK_REQUIRE(cluster_id || n == 0, ROGTK_E_INVALID, "cluster_id is NULL");
+    ROGTK_REQUIRE(n_clusters >= 0 && n_clusters < (1ll << 32) - 1, ROGTK_E_INVALID, "bad n_clusters %lld",
+                  (long long)n_clusters);
+    for (int64_t i = 0; i < n; ++i)
+        ROGTK_REQUIRE(!h.valid(i) || (int64_t)cluster_id[i] < n_clusters, ROGTK_E_INVALID,
+                      "cluster_id[%lld] = %u is >= n_clusters (%lld)", (long long)i, cluster_id[i],
+                      (long long)n_clusters);
+    const int L = umi_len > 0 ? umi_len : h.first_len();
+    HostCtx* c;
+    if (int rc = host_ctx(&c)) return rc;
+    int64_t max_len = 0;
+    if (n > 0) {
+        int Ls = 0;
+        if (int rc = upload_and_stage(c, h, L, &Ls, nullptr)) return rc;
+        if (int rc = device_max_len(c, h.ow, n, &max_len)) return rc;
+    }
+    if (int rc = c->out[0].ensure((size_t)std::max<int64_t>(n, 4) * 4)) return rc;
+    if (n > 0)
+        if (int rc = c->h2d(c->out[0].p, cluster_id, (size_t)n * 4)) return rc;
+    int rc = summary_to_host(c, c->offsets.p, h.ow, c->values.as<uint8_t>(),
+                             h.validity ? c->validity.as<uint8_t>() : nullptr, h.voff, n, L, c->out[0].as<uint32_t>(),
+                             n_clusters, max_len, representatives, n_reads, n_distinct);
+    if (rc) {
+        rogtk_str_result_free(representatives);
+        rogtk_u32_result_free(n_reads);
+        rogtk_u32_result_free(n_distinct);
+    }
+    return rc;
+}
+
+int rogtk_umi_correct_host(const rogtk_str_col* col, int umi_len, int max_distance, uint32_t* cluster_id,
+                           rogtk_str_result* corrected, rogtk_str_result* representatives, rogtk_u32_result* n_reads,
+                           rogtk_u32_result* n_distinct, int64_t* n_clusters, int* resolved_umi_len) {
+    if (int rc = check_correct_outputs(col, representatives, n_reads, n_distinct)) return rc;
+    ROGTK_REQUIRE(corrected, ROGTK_E_INVALID, "NULL output (corrected is required)");
+    *corrected = rogtk_str_result{};
+    HostCol h{col->offsets, col->offset_width, col->values, col->values_len, col->validity, col->validity_offset,
+              col->n};
+    if (int rc = check_host_col(h)) return rc;
+    const int64_t n = h.n;
+    ROGTK_REQUIRE(n < (1ll << 31), ROGTK_E_UNSUPPORTED, "umi_correct: at most 2^31 - 1 rows");
+    ROGTK_REQUIRE(cluster_id || n == 0, ROGTK_E_INVALID, "cluster_id is NULL");
+    ROGTK_REQUIRE(max_distance == 0 || max_distance == 1, ROGTK_E_UNSUPPORTED,
+                  "max_distance %d: only 0 and 1 are supported", max_distance);
+    int L = umi_len > 0 ? umi_len : h.first_len();
+    if (resolved_umi_len) *resolved_umi_len = L;
+    if (n_clusters) *n_clusters = 0;
+    HostCtx* c;
+    if (int rc = host_ctx(&c)) return rc;
+    auto run = [&]() -> int {
+        int64_t nclu = 0, max_len = 0;
+        if (int rc = c->out[0].ensure((size_t)std::max<int64_t>(n, 4) * 4)) return rc;
+        uint32_t* did = c->out[0].as<uint32_t>();
+        const uint8_t* dvalid = h.validity ? c->validity.as<uint8_t>() : nullptr;
+        if (n > 0) {
+            int64_t n_irr = 0;
+            if (int rc = upload_and_stage(c, h, L, &L, &n_irr)) return rc;
+            if (int rc = device_max_len(c, h.ow, n, &max_len)) return rc;
+            dvalid = h.validity ? c->validity.as<uint8_t>() : nullptr;
+            if (int rc = cluster_staged(c, c->offsets.p, h.ow, c->values.as<uint8_t>(), dvalid, h.voff, n, L, n_irr,
+                                        max_len, max_distance, did, &nclu, c->stream))
+                return rc;
+            if (int rc = c->d2h(cluster_id, did, (size_t)n * 4)) return rc;
+        }
+        if (n_clusters) *n_clusters = nclu;
+        if (int rc = summary_to_host(c, c->offsets.p, h.ow, c->values.as<uint8_t>(), dvalid, h.voff, n, L, did, nclu,
+                                     max_len, representatives, n_reads, n_distinct))
+            return rc;
+        // corrected: the input's offsets and nulls, every row's bytes from its representative
+        if (int rc = empty_str_result(n, corrected)) return rc;
+        for (int64_t i = 0; i <= n; ++i) corrected->offsets[i] = h.off(i);
+        for (int64_t i = 0; i < n; ++i) {
+            if (h.valid(i)) corrected->validity[i >> 3] |= (uint8_t)(1u << (i & 7));
+            else ++corrected->null_count;
+        }
+        const int64_t total = n > 0 ? h.off(n) : 0;
+        if (total > 0) {
+            free(corrected->values);
+            corrected->values = (uint8_t*)malloc((size_t)total);
+            ROGTK_REQUIRE(corrected->values, ROGTK_E_INVALID, "out of host memory for %lld output bytes",
+                          (long long)total);
+            corrected->values_len = total;
+            if (c->out[6].ensure((size_t)total)) return ROGTK_E_HIP;
+            ROGTK_HIP_CHECK(hipMemsetAsync(c->out[6].p, 0, (size_t)total, c->stream));
+            if (int rc = corrected_fill(c->offsets.p, h.ow, c->values.as<uint8_t>(), dvalid, h.voff, n, did, nclu,
+                                        c->out[3].as<int64_t>(), c->out[6].as<uint8_t>(), c->stream))
+                return rc;
+            if (int rc = c->d2h(corrected->values, c->out[6].p, (size_t)total)) return rc;
+        }
+        return ROGTK_OK;
+    };
+    const int rc = run();
+    if (rc) {
+        rogtk_str_result_free(corrected);
+        rogtk_str_result_free(representatives);
+        rogtk_u32_result_free(n_reads);
+        rogtk_u32_result_free(n_distinct);
+    }
+    return rc;
+}
+
+void rogtk_u32_result_free(rogtk_u32_result* r) {
+    if (!r) return;
+    free(r->data);
+    *r = rogtk_u32_result{0, nullptr};
+}
+
+int rogtk_cluster_summary_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
+                              int umi_len, const uint32_t* cluster_id, int64_t n_clusters, uint32_t* n_reads,
+                              uint32_t* n_distinct, int64_t* rep_rows, int64_t* rep_offsets, int64_t* rep_values_len,
+                              void* stream) {
+    ROGTK_REQUIRE(n >= 0 && n < (1ll << 31), ROGTK_E_UNSUPPORTED, "cluster_summary_dev: n %lld outside 0..2^31-1",
+                  (long long)n);
+    ROGTK_REQUIRE(n_clusters >= 0 && n_clusters < (1ll << 32) - 1, ROGTK_E_INVALID,
+                  "cluster_summary_dev: bad n_clusters %lld", (long long)n_clusters);
+    ROGTK_REQUIRE(n == 0 || (offsets && values && cluster_id), ROGTK_E_INVALID, "cluster_summary_dev: NULL input");
+    ROGTK_REQUIRE(n_reads && n_distinct && rep_rows && rep_offsets && rep_values_len, ROGTK_E_INVALID,
+                  "cluster_summary_dev: NULL output");
+    ROGTK_REQUIRE(umi_len >= 1, ROGTK_E_INVALID, "cluster_summary_dev: umi_len must be >= 1");
+    *rep_values_len = 0;
+    hipStream_t s = as_stream(stream);
+    HostCtx* c;
+    if (int rc = host_ctx(&c)) return rc;
+    int64_t max_len = 0;
+    if (n > 0) {
+        if (int rc = c->nirr.ensure(16)) return rc;
+        unsigned long long* slot = c->nirr.as<unsigned long long>() + 1;
+        ROGTK_HIP_CHECK(hipMemsetAsync(slot, 0, 8, s));
+        hipLaunchKernelGGL(k_max_len<int64_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, offsets, n, slot);
+        ROGTK_HIP_CHECK(hipGetLastError());
+        ROGTK_HIP_CHECK(hipMemcpyAsync(&max_len, slot, 8, hipMemcpyDeviceToHost, s));
+        ROGTK_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    if (int rc = cluster_summary_general(offsets, 8, values, validity, 0, n, umi_len, cluster_id, n_clusters, max_len,
+                                         n_reads, n_distinct, rep_rows, s))
+        return rc;
+    int64_t tb = 0;
+    if (int rc = representatives_temp(n_clusters, &tb)) return rc;
+    if (int rc = c->out[5].ensure((size_t)tb)) return rc;
+    if (int rc = representatives_measure(offsets, 8, rep_rows, n_clusters, rep_offsets, c->out[5].p, tb, s)) return rc;
+    ROGTK_HIP_CHECK(hipMemcpyAsync(rep_values_len, rep_offsets + n_clusters, 8, hipMemcpyDeviceToHost, s));
+    ROGTK_HIP_CHECK(hipStreamSynchronize(s));
+    return ROGTK_OK;
+}
+
+int rogtk_cluster_representatives_fill(const int64_t* offsets, const uint8_t* values, const int64_t* rep_rows,
+                                       int64_t n_clusters, const int64_t* rep_offsets, uint8_t* rep_values,
+                                       void* stream) {
+    ROGTK_REQUIRE(n_clusters >= 0, ROGTK_E_INVALID, "representatives_fill: negative n_clusters");
+    ROGTK_REQUIRE(n_clusters == 0 || (offsets && values && rep_rows && rep_offsets && rep_values), ROGTK_E_INVALID,
+                  "representatives_fill: NULL argument");
+    return representatives_fill(offsets, 8, values, rep_rows, n_clusters, rep_offsets, rep_values, as_stream(stream));
+}
+
+int rogtk_umi_correct_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
+                          int umi_len, int max_distance, uint32_t* cluster_id, int64_t* n_clusters,
+                          uint8_t* corrected_values, void* stream) {
+    ROGTK_REQUIRE(n >= 0 && n < (1ll << 31), ROGTK_E_UNSUPPORTED, "umi_correct_dev: n %lld outside 0..2^31-1",
+                  (long long)n);
+    ROGTK_REQUIRE(n == 0 || (offsets && values && cluster_id && corrected_values), ROGTK_E_INVALID,
+                  "umi_correct_dev: NULL argument");
+    ROGTK_REQUIRE(umi_len >= 1, ROGTK_E_INVALID, "umi_correct_dev: umi_len must be >= 1");
+    ROGTK_REQUIRE(max_distance == 0 || max_distance == 1, ROGTK_E_UNSUPPORTED,
+                  "max_distance %d: only 0 and 1 are supported", max_distance);
+    if (n_clusters) *n_clusters = 0;
+    if (n == 0) return ROGTK_OK;
+    hipStream_t s = as_stream(stream);
+    HostCtx* c;
+    if (int rc = host_ctx(&c)) return rc;
+    int64_t nclu = 0, max_len = 0;
+    if (int rc = cluster_dev(c, offsets, values, validity, n, umi_len, max_distance, cluster_id, &nclu, &max_len, s))
+        return rc;
+    if (n_clusters) *n_clusters = nclu;
+    const int64_t nc1 = std::max<int64_t>(nclu, 1);
+    if (c->out[1].ensure((size_t)nc1 * 4) || c->out[2].ensure((size_t)nc1 * 4) || c->out[3].ensure((size_t)nc1 * 8))
+        return ROGTK_E_HIP;
+    if (int rc = cluster_summary_general(offsets, 8, values, validity, 0, n, umi_len, cluster_id, nclu, max_len,
+                                         c->out[1].as<uint32_t>(), c->out[2].as<uint32_t>(), c->out[3].as<int64_t>(),
+                                         s))
+        return rc;
+    return corrected_fill(offsets, 8, values, validity, 0, n, cluster_id, nclu, c->out[3].as<int64_t>(),
+                          corrected_values, s);
 }
 
 // --------------------------------------------------------------- stream events

@@ -1053,6 +1053,31 @@ void fuzzy_expr(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* o
     export_series(out, {s.name, "b", {}}, std::move(chunks));
 }
 
+// ------------------------------------------------------------ UMI correction
+// umi_correct_expr (no reference counterpart): every chunk of the series as
+// ONE batch (the clusters are global to the column) -> the corrected UMI of every row.
+struct U32ResultHolder {
+    rogtk_u32_result r{};
+    ~U32ResultHolder() { rogtk_u32_result_free(&r); }
+};
+void umi_correct_expr(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out) {
+    if (n_in < 1) fail("expected one input series");
+    const int64_t umi_len = kw.opt_uint("umi_len", 0), maxd = kw.opt_uint("max_distance", 1);
+    if (umi_len > (1 << 30) || maxd > (1 << 30)) fail("could not parse kwargs: umi_len / max_distance out of range");
+    StrSeries s = str_series(in[0]);
+    FlatCol f = flatten_all(s);
+    const rogtk_str_col d = str_desc(f);
+    std::vector<uint32_t> ids((size_t)std::max<int64_t>(f.n, 1));
+    StrResultHolder corrected, reps;
+    U32ResultHolder n_reads, n_distinct;
+    int64_t n_clusters = 0;
+    check(rogtk_umi_correct_host(&d, (int)umi_len, (int)maxd, ids.data(), &corrected.r, &reps.r, &n_reads.r,
+                                 &n_distinct.r, &n_clusters, nullptr));
+    std::vector<Col> chunks;
+    chunks.push_back(view_col_result(corrected.r));
+    export_series(out, {s.name, "vu", {}}, std::move(chunks));
+}
+
 int64_t phred_base(const Kwargs& kw) {
     const int64_t b = kw.uint("base");  // Phred2NmKwargs.base: u8 (expressions.rs:493-496)
     if (b > 255) fail("could not parse kwargs: base does not fit in u8");
@@ -1251,5 +1276,9 @@ ROGTK_FIELD(fuzzy_contains_expr, (FieldSpec{name, "b", {}}))
 ROGTK_EXPR(fuzzy_replace_expr,
            fuzzy_expr(inputs, n_inputs, parse_kwargs(kwargs_ptr, kwargs_len), return_value, false, true))
 ROGTK_FIELD(fuzzy_replace_expr, (FieldSpec{name, "vu", {}}))
+
+// UMI correction: the representative UMI of every row's H3 cluster
+ROGTK_EXPR(umi_correct_expr, umi_correct_expr(inputs, n_inputs, parse_kwargs(kwargs_ptr, kwargs_len), return_value))
+ROGTK_FIELD(umi_correct_expr, (FieldSpec{name, "vu", {}}))
 
 }  // extern "C"

@@ -390,4 +390,31 @@ int long_cluster(const void* offsets, int ow, const uint8_t* values, const uint8
                  int64_t n, int L, int max_distance, int64_t max_len, uint32_t* cid, int64_t* n_clusters,
                  hipStream_t s);
 
+// ------------------------------------------------ UMI correction (correct.hip)
+// packed SoA: the three per-cluster tables from (codes, regular bits, ids); enqueue-only
+int cluster_summary_packed_temp(int64_t n, int L, int64_t n_clusters, int64_t* bytes);
+int launch_cluster_summary_packed(const uint32_t* codes, const uint64_t* regular_bits, int64_t n, int L,
+                                  const uint32_t* cluster_id, int64_t n_clusters, uint32_t* rep_code,
+                                  uint32_t* n_reads, uint32_t* n_distinct, void* temp, int64_t temp_bytes,
+                                  hipStream_t s);
+int launch_cluster_correct_packed(const uint32_t* cluster_id, const uint64_t* regular_bits, int64_t n,
+                                  const uint32_t* rep_code, int64_t n_clusters, uint32_t* corrected, hipStream_t s);
+int cluster_summary_set_method(int m);
+// any device string column: n_reads / n_distinct / rep_row[n_clusters] (a row that holds the
+// cluster's representative; -1 for a cluster without rows). Synchronises s (row counts);
+// ROGTK_E_INVALID when a non-null row's id is >= n_clusters.
+int cluster_summary_general(const void* offsets, int ow, const uint8_t* values, const uint8_t* validity, int64_t voff,
+                            int64_t n, int L, const uint32_t* ids, int64_t n_clusters, int64_t max_len,
+                            uint32_t* n_reads, uint32_t* n_distinct, int64_t* rep_row, hipStream_t s);
+// the representatives as a string column: measure (out_offsets[n_clusters + 1]) then fill
+int representatives_temp(int64_t n_clusters, int64_t* bytes);
+int representatives_measure(const void* offsets, int ow, const int64_t* rep_row, int64_t n_clusters,
+                            int64_t* out_offsets, void* temp, int64_t temp_bytes, hipStream_t s);
+int representatives_fill(const void* offsets, int ow, const uint8_t* values, const int64_t* rep_row, int64_t n_clusters,
+                         const int64_t* out_offsets, uint8_t* out_values, hipStream_t s);
+// corrected values under the input's own offsets (ids computed by the library)
+int corrected_fill(const void* offsets, int ow, const uint8_t* values, const uint8_t* validity, int64_t voff,
+                   int64_t n, const uint32_t* ids, int64_t n_clusters, const int64_t* rep_row, uint8_t* out_values,
+                   hipStream_t s);
+
 }  // namespace rogtk
