@@ -686,6 +686,57 @@ int rogtk_cluster_summary_host(const rogtk_str_col* col, int umi_len, const uint
                                rogtk_str_result* representatives, rogtk_u32_result* n_reads,
                                rogtk_u32_result* n_distinct);
 
+/* ====== Directional UMI clustering and correction (directional.hip; spec: DESIGN.md §4c) ======
+ * The count-aware grouping at one edit, UMI-tools' "directional" adjacency with its tie order
+ * made canonical. Vertices: the distinct regular strings (byte length umi_len 1..32, only
+ * ACGT), each with count = its rows. Directed edge a -> b when a and b differ at exactly one
+ * position and count(a) >= 2 * count(b) - 1 (64-bit). root(v) = the vertex of largest key
+ * (count, then the smaller 2-bit code) among all vertices that reach v, v included; a
+ * cluster = the vertices sharing a root, so the root is the cluster's representative under
+ * the §4b vote and every cluster lies inside one max_distance = 1 cluster. Irregular non-null
+ * strings take no edges: exact bytes, as max_distance = 0 (an N does not bridge clusters
+ * here, unlike rogtk_umi_cluster_host at max_distance = 1). Ids: dense; regular clusters in
+ * ascending order of their root's code, then the distinct irregular strings in
+ * byte-lexicographic order; 0xFFFFFFFF for null rows. n < 2^31 rows. */
+
+/* Level 1, codes: codes[m] ascending distinct 2-bit codes (first base in the highest digit),
+ * counts[m] their rows (device). Device outputs root[m] (index into codes) and labels[m];
+ * *n_clusters and *rounds (relaxation rounds up to and including the first that changed
+ * nothing, >= 1 for m >= 1) on the host. temp: device scratch of
+ * rogtk_directional_temp_bytes() bytes (12 * umi_len * m for the in-edge table, + 24 m).
+ * Synchronises `stream`. ROGTK_E_HIP if round m still changed something (never a partial
+ * answer). */
+int rogtk_directional_temp_bytes(int64_t m, int umi_len, int64_t* bytes);
+int rogtk_directional_codes(const uint64_t* codes, const uint32_t* counts, int64_t m, int umi_len,
+                            uint32_t* root /* [m] */, uint32_t* labels /* [m] */, int64_t* n_clusters,
+                            int64_t* rounds, void* temp, int64_t temp_bytes, void* stream);
+/* *rounds of this thread's last directional call (any entry point below; 0: no regular row). */
+int rogtk_directional_last_rounds(int64_t* rounds);
+
+/* Level 1, device column (layout as rogtk_umi_cluster_dev). cluster_id[n] (device),
+ * *n_clusters (host); root_code (nullable, device, [n]): the 2-bit code of the row's root,
+ * all ones for a row that is null or irregular (at umi_len 32 that is also the all-T code:
+ * tell them apart by the row). Synchronises `stream`. */
+int rogtk_umi_cluster_directional_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
+                                      int umi_len, uint32_t* cluster_id, int64_t* n_clusters, uint64_t* root_code,
+                                      void* stream);
+/* rogtk_umi_correct_dev with directional ids: ids, then the §4b summary and gather. */
+int rogtk_umi_correct_directional_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
+                                      int umi_len, uint32_t* cluster_id, int64_t* n_clusters,
+                                      uint8_t* corrected_values, void* stream);
+
+/* Level 2, host column: arguments and outputs exactly those of rogtk_umi_cluster_host /
+ * rogtk_umi_correct_host. max_distance 1: the rule above; 0: no edges, the same call of the
+ * transitive entry; anything else ROGTK_E_UNSUPPORTED, before any device work. */
+int rogtk_umi_cluster_directional_host(const void* offsets, int offset_width, const uint8_t* values, int64_t values_len,
+                                       const uint8_t* validity, int64_t validity_offset, int64_t n, int umi_len,
+                                       int max_distance, uint32_t* cluster_id, int64_t* n_clusters,
+                                       int* resolved_umi_len);
+int rogtk_umi_correct_directional_host(const rogtk_str_col* col, int umi_len, int max_distance, uint32_t* cluster_id,
+                                       rogtk_str_result* corrected, rogtk_str_result* representatives,
+                                       rogtk_u32_result* n_reads, rogtk_u32_result* n_distinct, int64_t* n_clusters,
+                                       int* resolved_umi_len);
+
 /* ============================== profiling ================================ */
 /* When enabled, every kernel launch is bracketed by HIP events on its stream. */
 /* ======== multi-GPU exchange of read groups ========
@@ -817,7 +868,8 @@ int rogtk_copy(void* dst, const void* src, int64_t bytes, void* stream);
  * (:1048-1101), assemble_sequences_expr (:695), assemble_sequences_with_anchors_expr
  * (:770), sweep_assembly_params_expr (:880), optimize_assembly_expr
  * (fracture_opt.rs:283), and umi_correct_expr (no reference counterpart: the corrected UMI
- * of every row, kwargs umi_len / max_distance, the whole series one batch). The structs are the Arrow C Data Interface and polars-ffi
+ * of every row, kwargs umi_len / max_distance / method ("cluster", the default, or
+ * "directional"), the whole series one batch). The structs are the Arrow C Data Interface and polars-ffi
  * version_0's SeriesExport {ArrowSchema* field; ArrowArray** arrays; size_t len;
  * void (*release)(SeriesExport*); void* private_data;}; see INTEGRATION.md.
  * Diagnostics: the kwargs pickle as the plugin parses it, "key=value" lines. */

@@ -226,6 +226,16 @@ SIGNATURES = {
                                _P_I64, _P_I32],
     "rogtk_cluster_summary_host": [ctypes.POINTER(StrCol), _i32, _vp, _i64, ctypes.POINTER(StrResult),
                                    ctypes.POINTER(U32Result), ctypes.POINTER(U32Result)],
+    "rogtk_directional_temp_bytes": [_i64, _i32, _P_I64],
+    "rogtk_directional_codes": [_vp, _vp, _i64, _i32, _vp, _vp, _P_I64, _P_I64, _vp, _i64, _vp],
+    "rogtk_directional_last_rounds": [_P_I64],
+    "rogtk_umi_cluster_directional_dev": [_vp, _vp, _vp, _i64, _i32, _vp, _P_I64, _vp, _vp],
+    "rogtk_umi_correct_directional_dev": [_vp, _vp, _vp, _i64, _i32, _vp, _P_I64, _vp, _vp],
+    "rogtk_umi_cluster_directional_host": [_vp, _i32, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _P_I64,
+                                           _P_I32],
+    "rogtk_umi_correct_directional_host": [ctypes.POINTER(StrCol), _i32, _i32, _vp, ctypes.POINTER(StrResult),
+                                           ctypes.POINTER(StrResult), ctypes.POINTER(U32Result),
+                                           ctypes.POINTER(U32Result), _P_I64, _P_I32],
     "rogtk_profile_enable": [_i32],
     "rogtk_profile_select": [ctypes.c_char_p],
     "rogtk_profile_reset": [],

@@ -161,12 +161,30 @@ def _hamming(column, target, max_distance, want_dist):
     return concat(arrays, pa.uint32() if want_dist else pa.bool_())
 
 
-def umi_cluster(column: ColumnLike, umi_len: int = 0, max_distance: int = 1):
+UMI_METHODS = ("cluster", "directional")
+
+
+def umi_method_entry(method: str, max_distance: int, cluster_entry: str, directional_entry: str) -> str:
+    """The C entry point of ``method``; any other string is a ValueError. The
+    directional entries' max_distance error is raised here, before any buffer is allocated."""
+    if method not in UMI_METHODS:
+        raise ValueError(f"method must be one of {UMI_METHODS}, got {method!r}")
+    if method == "cluster":
+        return cluster_entry
+    if int(max_distance) not in (0, 1):
+        raise _lib.RogtkError(_lib.ROGTK_E_UNSUPPORTED, f"max_distance {max_distance}: only 0 and 1 are supported")
+    return directional_entry
+
+
+def umi_cluster(column: ColumnLike, umi_len: int = 0, max_distance: int = 1, method: str = "cluster"):
     """H3 cluster id per row: dense ids, exact (0) or Hamming<=1 components (1).
+    method="directional": the count-aware rule at one edit; an abundant UMI
+    absorbs a neighbour only when count(abundant) >= 2 * count(neighbour) - 1.
 
     Returns (pa.UInt32Array with nulls for null rows, n_clusters, resolved umi_len).
     A multi-chunk column is clustered as one batch (ids are global to the column).
     """
+    entry = umi_method_entry(method, max_distance, "rogtk_umi_cluster_host", "rogtk_umi_cluster_directional_host")
     arr = column
     if isinstance(arr, pa.ChunkedArray):
         arr = arr.combine_chunks() if arr.num_chunks else pa.array([], type=arr.type)
@@ -178,7 +196,7 @@ def umi_cluster(column: ColumnLike, umi_len: int = 0, max_distance: int = 1):
     nclu = ctypes.c_int64(0)
     rl = ctypes.c_int(0)
     o, v, val = ch.ptrs()
-    _lib.call("rogtk_umi_cluster_host", o, ch.offset_width, v, ch.values.size, val, ch.validity_offset,
+    _lib.call(entry, o, ch.offset_width, v, ch.values.size, val, ch.validity_offset,
               n, int(umi_len), int(max_distance), _ptr(cid), ctypes.byref(nclu), ctypes.byref(rl))
     out = pa.Array.from_buffers(pa.uint32(), n, [validity_buffer(ch), pa.py_buffer(cid)])
     return out, int(nclu.value), int(rl.value)
@@ -259,16 +277,16 @@ class UmiNamespace:
     def dust_score(self):
         return self._one("dust_score")
 
-    def cluster(self, umi_len: int = 0, max_distance: int = 1):
-        """Extension (no reference counterpart): H3 cluster ids."""
-        return umi_cluster(self._c, umi_len, max_distance)[0]
+    def cluster(self, umi_len: int = 0, max_distance: int = 1, method: str = "cluster"):
+        """Extension (no reference counterpart): H3 cluster ids ("directional": DESIGN.md §4c)."""
+        return umi_cluster(self._c, umi_len, max_distance, method)[0]
 
-    def correct(self, umi_len: int = 0, max_distance: int = 1):
+    def correct(self, umi_len: int = 0, max_distance: int = 1, method: str = "cluster"):
         """Extension (no reference counterpart): every row's UMI replaced by the
-        representative of its H3 cluster."""
+        representative of its cluster (method="directional": §4c)."""
         from .correct import umi_correct
 
-        return umi_correct(self._c, umi_len, max_distance).corrected
+        return umi_correct(self._c, umi_len, max_distance, method).corrected
 
 
 class HammingExpr:

@@ -14,6 +14,7 @@ host (rogtk/__init__.py:206-214).
     res.clusters        # StructArray{representative, n_reads, n_distinct}, cluster-id order
     rg.umi_cluster_summary(umis, my_ids)          # the same table for the caller's ids
     rg.col(umis).umi.correct(max_distance=1)      # the corrected column alone
+    rg.umi_correct(umis, method="directional")    # count-aware clusters
 """
 from __future__ import annotations
 
@@ -84,9 +85,14 @@ def _clusters(reps, n_reads, n_distinct, typ) -> pa.StructArray:
                                       names=list(CLUSTER_FIELDS))
 
 
-def umi_correct(column: ColumnLike, umi_len: int = 0, max_distance: int = 1) -> UmiCorrection:
-    """H3 clusters of the column (as ``umi_cluster``), their summary and the corrected UMI
-    of every row. A multi-chunk column is one batch."""
+def umi_correct(column: ColumnLike, umi_len: int = 0, max_distance: int = 1,
+                method: str = "cluster") -> UmiCorrection:
+    """Clusters of the column (as ``umi_cluster``: method="cluster" the H3 components,
+    "directional" the count-aware rule of DESIGN.md §4c), their summary and the corrected
+    UMI of every row. A multi-chunk column is one batch."""
+    from .api import umi_method_entry
+
+    entry = umi_method_entry(method, max_distance, "rogtk_umi_correct_host", "rogtk_umi_correct_directional_host")
     ch = _one_chunk(column)
     n = ch.n
     cid = np.zeros(max(n, 1), dtype=np.uint32)
@@ -95,10 +101,10 @@ def umi_correct(column: ColumnLike, umi_len: int = 0, max_distance: int = 1) -> 
     nclu, rl = ctypes.c_int64(0), ctypes.c_int(0)
     desc = _desc(ch)
     lib = _lib.hip()
-    _lib.check(lib.rogtk_umi_correct_host(ctypes.byref(desc), int(umi_len), int(max_distance),
-                                          ctypes.c_void_p(cid.ctypes.data), ctypes.byref(corrected),
-                                          ctypes.byref(reps), ctypes.byref(n_reads), ctypes.byref(n_distinct),
-                                          ctypes.byref(nclu), ctypes.byref(rl)))
+    _lib.check(getattr(lib, entry)(ctypes.byref(desc), int(umi_len), int(max_distance),
+                                   ctypes.c_void_p(cid.ctypes.data), ctypes.byref(corrected),
+                                   ctypes.byref(reps), ctypes.byref(n_reads), ctypes.byref(n_distinct),
+                                   ctypes.byref(nclu), ctypes.byref(rl)))
     try:
         typ = _text_type(ch)
         out = _take_str(corrected, typ)

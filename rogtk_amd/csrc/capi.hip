@@ -1304,9 +1304,14 @@ int rogtk_cluster_summary_host(const rogtk_str_col* col, int umi_len, const uint
     return rc;
 }
 
-int rogtk_umi_correct_host(const rogtk_str_col* col, int umi_len, int max_distance, uint32_t* cluster_id,
-                           rogtk_str_result* corrected, rogtk_str_result* representatives, rogtk_u32_result* n_reads,
-                           rogtk_u32_result* n_distinct, int64_t* n_clusters, int* resolved_umi_len) {
+namespace {
+thread_local int64_t t_directional_rounds = 0;  // rogtk_directional_last_rounds
+
+// rogtk_umi_correct_host (directional = false) and rogtk_umi_correct_directional_host at
+// max_distance 1 (directional = true): they differ in the ids alone.
+static int correct_host(const rogtk_str_col* col, int umi_len, int max_distance, bool directional, uint32_t* cluster_id,
+                        rogtk_str_result* corrected, rogtk_str_result* representatives, rogtk_u32_result* n_reads,
+                        rogtk_u32_result* n_distinct, int64_t* n_clusters, int* resolved_umi_len) {
     if (int rc = check_correct_outputs(col, representatives, n_reads, n_distinct)) return rc;
     ROGTK_REQUIRE(corrected, ROGTK_E_INVALID, "NULL output (corrected is required)");
     *corrected = rogtk_str_result{};
@@ -1333,9 +1338,14 @@ int rogtk_umi_correct_host(const rogtk_str_col* col, int umi_len, int max_distan
             if (int rc = upload_and_stage(c, h, L, &L, &n_irr)) return rc;
             if (int rc = device_max_len(c, h.ow, n, &max_len)) return rc;
             dvalid = h.validity ? c->validity.as<uint8_t>() : nullptr;
-            if (int rc = cluster_staged(c, c->offsets.p, h.ow, c->values.as<uint8_t>(), dvalid, h.voff, n, L, n_irr,
-                                        max_len, max_distance, did, &nclu, c->stream))
+            if (directional) {
+                if (int rc = directional_cluster(c->offsets.p, h.ow, c->values.as<uint8_t>(), dvalid, h.voff, n, L,
+                                                 did, nullptr, &nclu, &t_directional_rounds, nullptr, c->stream))
+                    return rc;
+            } else if (int rc = cluster_staged(c, c->offsets.p, h.ow, c->values.as<uint8_t>(), dvalid, h.voff, n, L,
+                                               n_irr, max_len, max_distance, did, &nclu, c->stream)) {
                 return rc;
+            }
             if (int rc = c->d2h(cluster_id, did, (size_t)n * 4)) return rc;
         }
         if (n_clusters) *n_clusters = nclu;
@@ -1373,6 +1383,15 @@ int rogtk_umi_correct_host(const rogtk_str_col* col, int umi_len, int max_distan
         rogtk_u32_result_free(n_distinct);
     }
     return rc;
+}
+
+}  // namespace
+
+int rogtk_umi_correct_host(const rogtk_str_col* col, int umi_len, int max_distance, uint32_t* cluster_id,
+                           rogtk_str_result* corrected, rogtk_str_result* representatives, rogtk_u32_result* n_reads,
+                           rogtk_u32_result* n_distinct, int64_t* n_clusters, int* resolved_umi_len) {
+    return correct_host(col, umi_len, max_distance, false, cluster_id, corrected, representatives, n_reads, n_distinct,
+                        n_clusters, resolved_umi_len);
 }
 
 void rogtk_u32_result_free(rogtk_u32_result* r) {
@@ -1456,6 +1475,124 @@ int rogtk_umi_correct_dev(const int64_t* offsets, const uint8_t* values, const u
         return rc;
     return corrected_fill(offsets, 8, values, validity, 0, n, cluster_id, nclu, c->out[3].as<int64_t>(),
                           corrected_values, s);
+}
+
+// ------------------------------------ directional UMI clustering (directional.hip)
+int rogtk_directional_temp_bytes(int64_t m, int umi_len, int64_t* bytes) {
+    ROGTK_REQUIRE(bytes, ROGTK_E_INVALID, "directional_temp_bytes: NULL bytes");
+    ROGTK_REQUIRE(umi_len >= 1 && umi_len <= 32, ROGTK_E_UNSUPPORTED, "directional: umi_len %d outside 1..32", umi_len);
+    ROGTK_REQUIRE(m >= 0 && m < (1ll << 31), ROGTK_E_UNSUPPORTED, "directional: m %lld outside 0..2^31-1",
+                  (long long)m);
+    return directional_codes_temp(m, umi_len, bytes);
+}
+
+int rogtk_directional_codes(const uint64_t* codes, const uint32_t* counts, int64_t m, int umi_len, uint32_t* root,
+                            uint32_t* labels, int64_t* n_clusters, int64_t* rounds, void* temp, int64_t temp_bytes,
+                            void* stream) {
+    ROGTK_REQUIRE(umi_len >= 1 && umi_len <= 32, ROGTK_E_UNSUPPORTED, "directional: umi_len %d outside 1..32", umi_len);
+    ROGTK_REQUIRE(m >= 0 && m < (1ll << 31), ROGTK_E_UNSUPPORTED, "directional: m %lld outside 0..2^31-1",
+                  (long long)m);
+    ROGTK_REQUIRE(n_clusters && rounds, ROGTK_E_INVALID, "directional: NULL n_clusters / rounds");
+    ROGTK_REQUIRE(m == 0 || (codes && counts && root && labels && temp), ROGTK_E_INVALID, "directional: NULL argument");
+    const int rc = directional_codes(codes, counts, m, umi_len, root, labels, n_clusters, rounds, temp, temp_bytes,
+                                     as_stream(stream));
+    t_directional_rounds = *rounds;
+    return rc;
+}
+
+int rogtk_directional_last_rounds(int64_t* rounds) {
+    ROGTK_REQUIRE(rounds, ROGTK_E_INVALID, "directional_last_rounds: NULL rounds");
+    *rounds = t_directional_rounds;
+    return ROGTK_OK;
+}
+
+int rogtk_umi_cluster_directional_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
+                                      int umi_len, uint32_t* cluster_id, int64_t* n_clusters, uint64_t* root_code,
+                                      void* stream) {
+    ROGTK_REQUIRE(n >= 0 && n < (1ll << 31), ROGTK_E_UNSUPPORTED, "umi_cluster_directional_dev: n %lld outside 0..2^31-1",
+                  (long long)n);
+    ROGTK_REQUIRE(n == 0 || (offsets && values && cluster_id), ROGTK_E_INVALID,
+                  "umi_cluster_directional_dev: NULL argument");
+    ROGTK_REQUIRE(umi_len >= 1, ROGTK_E_INVALID, "umi_cluster_directional_dev: umi_len must be >= 1");
+    int64_t nclu = 0;
+    t_directional_rounds = 0;
+    if (n_clusters) *n_clusters = 0;
+    if (n == 0) return ROGTK_OK;
+    if (int rc = directional_cluster(offsets, 8, values, validity, 0, n, umi_len, cluster_id, root_code, &nclu,
+                                     &t_directional_rounds, nullptr, as_stream(stream)))
+        return rc;
+    if (n_clusters) *n_clusters = nclu;
+    return ROGTK_OK;
+}
+
+int rogtk_umi_correct_directional_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
+                                      int umi_len, uint32_t* cluster_id, int64_t* n_clusters,
+                                      uint8_t* corrected_values, void* stream) {
+    ROGTK_REQUIRE(n >= 0 && n < (1ll << 31), ROGTK_E_UNSUPPORTED, "umi_correct_directional_dev: n %lld outside 0..2^31-1",
+                  (long long)n);
+    ROGTK_REQUIRE(n == 0 || (offsets && values && cluster_id && corrected_values), ROGTK_E_INVALID,
+                  "umi_correct_directional_dev: NULL argument");
+    ROGTK_REQUIRE(umi_len >= 1, ROGTK_E_INVALID, "umi_correct_directional_dev: umi_len must be >= 1");
+    if (n_clusters) *n_clusters = 0;
+    t_directional_rounds = 0;
+    if (n == 0) return ROGTK_OK;
+    hipStream_t s = as_stream(stream);
+    HostCtx* c;
+    if (int rc = host_ctx(&c)) return rc;
+    int64_t nclu = 0, max_len = 0;
+    if (int rc = directional_cluster(offsets, 8, values, validity, 0, n, umi_len, cluster_id, nullptr, &nclu,
+                                     &t_directional_rounds, &max_len, s))
+        return rc;
+    if (n_clusters) *n_clusters = nclu;
+    const int64_t nc1 = std::max<int64_t>(nclu, 1);
+    if (c->out[1].ensure((size_t)nc1 * 4) || c->out[2].ensure((size_t)nc1 * 4) || c->out[3].ensure((size_t)nc1 * 8))
+        return ROGTK_E_HIP;
+    if (int rc = cluster_summary_general(offsets, 8, values, validity, 0, n, umi_len, cluster_id, nclu, max_len,
+                                         c->out[1].as<uint32_t>(), c->out[2].as<uint32_t>(), c->out[3].as<int64_t>(),
+                                         s))
+        return rc;
+    return corrected_fill(offsets, 8, values, validity, 0, n, cluster_id, nclu, c->out[3].as<int64_t>(),
+                          corrected_values, s);
+}
+
+int rogtk_umi_cluster_directional_host(const void* offsets, int offset_width, const uint8_t* values, int64_t values_len,
+                                       const uint8_t* validity, int64_t validity_offset, int64_t n, int umi_len,
+                                       int max_distance, uint32_t* cluster_id, int64_t* n_clusters,
+                                       int* resolved_umi_len) {
+    ROGTK_REQUIRE(max_distance == 0 || max_distance == 1, ROGTK_E_UNSUPPORTED,
+                  "max_distance %d: only 0 and 1 are supported", max_distance);
+    if (max_distance == 0)  // no edges: the exact grouping, one implementation
+        return rogtk_umi_cluster_host(offsets, offset_width, values, values_len, validity, validity_offset, n, umi_len,
+                                      0, cluster_id, n_clusters, resolved_umi_len);
+    HostCol h{offsets, offset_width, values, values_len, validity, validity_offset, n};
+    if (int rc = check_host_col(h)) return rc;
+    ROGTK_REQUIRE(n < (1ll << 31), ROGTK_E_UNSUPPORTED, "umi_cluster_directional: at most 2^31 - 1 rows");
+    ROGTK_REQUIRE(cluster_id || n == 0, ROGTK_E_INVALID, "cluster_id is NULL");
+    int L = umi_len > 0 ? umi_len : h.first_len();
+    if (resolved_umi_len) *resolved_umi_len = L;
+    if (n_clusters) *n_clusters = 0;
+    t_directional_rounds = 0;
+    if (n == 0) return ROGTK_OK;
+    HostCtx* c;
+    if (int rc = host_ctx(&c)) return rc;
+    if (int rc = upload_and_stage(c, h, L, &L, nullptr)) return rc;
+    if (int rc = c->out[0].ensure((size_t)std::max<int64_t>(n, 4) * 4)) return rc;
+    uint32_t* did = c->out[0].as<uint32_t>();
+    int64_t nclu = 0;
+    if (int rc = directional_cluster(c->offsets.p, offset_width, c->values.as<uint8_t>(),
+                                     h.validity ? c->validity.as<uint8_t>() : nullptr, h.voff, n, L, did, nullptr,
+                                     &nclu, &t_directional_rounds, nullptr, c->stream))
+        return rc;
+    if (n_clusters) *n_clusters = nclu;
+    return c->d2h(cluster_id, did, (size_t)n * 4);
+}
+
+int rogtk_umi_correct_directional_host(const rogtk_str_col* col, int umi_len, int max_distance, uint32_t* cluster_id,
+                                       rogtk_str_result* corrected, rogtk_str_result* representatives,
+                                       rogtk_u32_result* n_reads, rogtk_u32_result* n_distinct, int64_t* n_clusters,
+                                       int* resolved_umi_len) {
+    return correct_host(col, umi_len, max_distance, max_distance == 1, cluster_id, corrected, representatives, n_reads,
+                        n_distinct, n_clusters, resolved_umi_len);
 }
 
 // --------------------------------------------------------------- stream events

@@ -1,0 +1,471 @@
+// directional.hip — count-aware ("directional") UMI clustering on gfx950.
+//
+// Vertices are the distinct regular strings (byte length L, only ACGT, L 1..32) as 2-bit
+// codes, first base in the highest digit, each with count = its rows. There is a directed
+// edge a -> b when the codes differ in exactly one digit and count(a) >= 2 count(b) - 1.
+// root(v) is the vertex of largest key (count, then the smaller code) among all vertices
+// that reach v, v included; a cluster is the set of vertices sharing a root. Irregular
+// strings take no edges and are grouped by exact bytes (irregular.hip), after the regular
+// clusters.
+//
+//   count   the regular rows' (code, row) pairs, compacted and radix-sorted over the 2 L
+//           code bits (u32 keys for L <= 16, u64 above); heads of runs of equal codes,
+//           scanned, give the sorted distinct codes D[m], their counts C[m] and every
+//           sorted row's index into D.
+//   edges   one lane per distinct code v probes its 3 L one-substitution neighbours in D
+//           by binary search (two distinct integers d apart in value are at most d apart
+//           in a sorted array of distinct integers, which bounds the search window: the
+//           low digits need 2-4 steps) and keeps the in-neighbours u that pass the count
+//           test, adj[k * m + v] = u for k < deg[v]. Stored once; the rounds do not
+//           search again. The table is 3 L columns of m entries, so lanes read it
+//           coalesced, and one search pass fills it (a compacted CSR needs a second one).
+//   relax   best[v] = max(best[v], best[u] over in-neighbours u, best[root of best[v]]),
+//           on the u64 key count << 32 | (0xFFFFFFFF - index in D): D ascends, so the
+//           smaller index is the smaller code. In place: the update is monotone and every
+//           value a lane can read is the key of an ancestor, so a stale read only delays
+//           a round and the fixed point is the same however lanes interleave. A round that
+//           improves nothing ends the loop (directional_rounds.h).
+//   label   flag best[v] == key(v), scan in D order, labels[v] = rank of v's root.
+#include <hipcub/hipcub.hpp>
+
+#include "directional_rounds.h"
+#include "rogtk_internal.h"
+
+namespace rogtk {
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kPackRows = 4;  // rows per thread of k_dir_pack
+constexpr int kPackTile = kBlock * kPackRows;
+constexpr int kCtrlWords = 64;  // [0, kDirBatch): changed words; [8]: cluster count
+
+inline size_t al(size_t b) { return (std::max<size_t>(b, 1) + 255) / 256 * 256; }
+inline unsigned grid_for(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + kBlock - 1) / kBlock); }
+
+template <int OW>
+__device__ __forceinline__ void span(const void* offs, int64_t row, int64_t& st, int64_t& len) {
+    if (OW == 4) {
+        const int32_t* o = (const int32_t*)offs;
+        st = o[row];
+        len = (int64_t)o[row + 1] - o[row];
+    } else {
+        const int64_t* o = (const int64_t*)offs;
+        st = o[row];
+        len = o[row + 1] - o[row];
+    }
+}
+
+__device__ __forceinline__ int base_code(uint8_t ch) {
+    return ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : -1;
+}
+
+// ------------------------------------------------------------------- count
+// Regular rows' (code, row) pairs appended to key / row, the irregular non-null rows to irr,
+// in any order (both are sorted later). A workgroup classifies kPackTile rows and reserves
+// its two ranges with one atomic each: cnt[0] regular rows, cnt[1] irregular rows; cnt[2] =
+// the longest irregular row.
+template <int OW, class K>
+__global__ void __launch_bounds__(kBlock)
+k_dir_pack(const void* __restrict__ offs, const uint8_t* __restrict__ vals, const uint8_t* __restrict__ validity,
+           int64_t voff, int64_t n, int L, K* __restrict__ key, uint32_t* __restrict__ row,
+           int64_t* __restrict__ irr, unsigned long long* __restrict__ cnt) {
+    constexpr int kWaves = kBlock / 64;
+    __shared__ uint32_t pre_r[kPackRows * kWaves], pre_i[kPackRows * kWaves];
+    __shared__ unsigned long long base[2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t tile = (int64_t)blockIdx.x * kPackTile;
+    uint64_t code[kPackRows], rmask[kPackRows], imask[kPackRows];
+    unsigned long long longest = 0;
+    for (int r = 0; r < kPackRows; ++r) {
+        const int64_t i = tile + (int64_t)r * kBlock + threadIdx.x;
+        bool valid = false, regular = false;
+        uint64_t c = 0;
+        if (i < n) {
+            valid = true;
+            if (validity) {
+                const int64_t b = voff + i;
+                valid = (validity[b >> 3] >> (b & 7)) & 1;
+            }
+            if (valid) {
+                int64_t st, len;
+                span<OW>(offs, i, st, len);
+                regular = L >= 1 && L <= 32 && len == L;
+                for (int j = 0; regular && j < L; ++j) {
+                    const int b = base_code(vals[st + j]);
+                    regular = b >= 0;
+                    c = (c << 2) | (uint64_t)(b & 3);
+                }
+                if (!regular) longest = max(longest, (unsigned long long)len);
+            }
+        }
+        code[r] = c;
+        rmask[r] = __ballot(regular);
+        imask[r] = __ballot(valid && !regular);
+        if (lane == 0) {
+            pre_r[r * kWaves + wave] = (uint32_t)__popcll(rmask[r]);
+            pre_i[r * kWaves + wave] = (uint32_t)__popcll(imask[r]);
+        }
+    }
+    for (int d = 32; d; d >>= 1) longest = max(longest, (unsigned long long)__shfl_xor(longest, d));
+    if (lane == 0 && longest) atomicMax(&cnt[2], longest);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t sr = 0, si = 0;
+        for (int k = 0; k < kPackRows * kWaves; ++k) {
+            const uint32_t cr = pre_r[k], ci = pre_i[k];
+            pre_r[k] = sr;
+            pre_i[k] = si;
+            sr += cr;
+            si += ci;
+        }
+        base[0] = sr ? atomicAdd(&cnt[0], (unsigned long long)sr) : 0ull;
+        base[1] = si ? atomicAdd(&cnt[1], (unsigned long long)si) : 0ull;
+    }
+    __syncthreads();
+    const uint64_t below = (1ull << lane) - 1ull;
+    for (int r = 0; r < kPackRows; ++r) {
+        const int64_t i = tile + (int64_t)r * kBlock + threadIdx.x;
+        if ((rmask[r] >> lane) & 1ull) {
+            const int64_t p = (int64_t)base[0] + pre_r[r * kWaves + wave] + __popcll(rmask[r] & below);
+            key[p] = (K)code[r];
+            row[p] = (uint32_t)i;
+        } else if ((imask[r] >> lane) & 1ull) {
+            irr[(int64_t)base[1] + pre_i[r * kWaves + wave] + __popcll(imask[r] & below)] = i;
+        }
+    }
+}
+
+template <class K>
+__global__ void k_dir_heads(const K* __restrict__ key, int64_t n, uint32_t* __restrict__ flag) {
+    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (k >= n) return;
+    flag[k] = k == 0 || key[k - 1] != key[k];
+}
+
+// pos = inclusive scan of the head flags: the head of run j (pos j + 1) names D[j]
+template <class K>
+__global__ void k_dir_distinct(const K* __restrict__ key, const uint32_t* __restrict__ flag,
+                               const uint32_t* __restrict__ pos, int64_t n, uint64_t* __restrict__ D,
+                               uint32_t* __restrict__ head) {
+    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (k >= n || !flag[k]) return;
+    D[pos[k] - 1] = (uint64_t)key[k];
+    head[pos[k] - 1] = (uint32_t)k;
+}
+
+__global__ void k_dir_counts(const uint32_t* __restrict__ head, int64_t m, int64_t n, uint32_t* __restrict__ C) {
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= m) return;
+    C[j] = (j + 1 < m ? head[j + 1] : (uint32_t)n) - head[j];
+}
+
+// ------------------------------------------------------------------- edges
+__device__ __forceinline__ unsigned long long dir_key(uint32_t count, uint32_t v) {
+    return ((unsigned long long)count << 32) | (unsigned long long)(0xFFFFFFFFu - v);
+}
+__device__ __forceinline__ uint32_t dir_index(unsigned long long key) { return 0xFFFFFFFFu - (uint32_t)key; }
+
+__global__ void __launch_bounds__(kBlock)
+k_dir_edges(const uint64_t* __restrict__ D, const uint32_t* __restrict__ C, int64_t m, int L,
+            uint32_t* __restrict__ deg, uint32_t* __restrict__ adj, unsigned long long* __restrict__ best) {
+    const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (v >= m) return;
+    const uint64_t code = D[v];
+    const uint32_t cv = C[v];
+    const uint64_t need = 2ull * (uint64_t)cv - 1ull;  // count(u) >= 2 count(v) - 1, in 64 bits
+    uint32_t nd = 0;
+    for (int p = 0; p < L; ++p) {
+        for (uint64_t x = 1; x <= 3; ++x) {
+            const uint64_t q = code ^ (x << (2 * p));
+            // |index(q) - v| <= |q - code|: the codes between them are distinct integers
+            int64_t lo, hi;
+            if (q < code) {
+                const uint64_t d = code - q;
+                lo = d < (uint64_t)v ? v - (int64_t)d : 0;
+                hi = v;
+            } else {
+                const uint64_t d = q - code;
+                lo = v + 1;
+                hi = d < (uint64_t)(m - v) ? v + (int64_t)d + 1 : m;
+            }
+            while (lo < hi) {  // first index in [lo, hi) with D[index] >= q
+                const int64_t mid = (lo + hi) >> 1;
+                if (D[mid] < q) lo = mid + 1;
+                else hi = mid;
+            }
+            if (lo < m && D[lo] == q && (uint64_t)C[lo] >= need) {
+                adj[(int64_t)nd * m + v] = (uint32_t)lo;
+                ++nd;
+            }
+        }
+    }
+    deg[v] = nd;
+    best[v] = dir_key(cv, (uint32_t)v);
+}
+
+// ------------------------------------------------------------------- relax
+// One round, in place. best[] is read and written by other workgroups in the same launch:
+// relaxed agent-scope accesses keep each 8-byte key whole, and any value read, however
+// stale, is the key of an ancestor (see the header comment), so no ordering is needed.
+__device__ __forceinline__ unsigned long long best_load(const unsigned long long* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__global__ void __launch_bounds__(kBlock)
+k_dir_relax(const uint32_t* __restrict__ deg, const uint32_t* __restrict__ adj, int64_t m,
+            unsigned long long* best, uint32_t* changed) {
+    const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    bool moved = false;
+    if (v < m) {
+        const unsigned long long old = best_load(best + v);
+        unsigned long long b = old;
+        const uint32_t nd = deg[v];
+        for (uint32_t k = 0; k < nd; ++k) b = max(b, best_load(best + adj[(int64_t)k * m + v]));
+        b = max(b, best_load(best + dir_index(b)));  // an ancestor's ancestor is an ancestor
+        if (b != old) {
+            __hip_atomic_store(best + v, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            moved = true;
+        }
+    }
+    if (__ballot(moved) && (threadIdx.x & 63) == 0) *changed = 1u;
+}
+
+// ------------------------------------------------------------------- label
+__global__ void k_dir_roots(const unsigned long long* __restrict__ best, int64_t m, uint32_t* __restrict__ root,
+                            uint32_t* __restrict__ flag) {
+    const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (v >= m) return;
+    const uint32_t r = dir_index(best[v]);
+    root[v] = r;
+    flag[v] = r == (uint32_t)v;
+}
+
+__global__ void k_dir_labels(const uint32_t* __restrict__ root, const uint32_t* __restrict__ flag,
+                             const uint32_t* __restrict__ rank, int64_t m, uint32_t* __restrict__ labels,
+                             uint32_t* __restrict__ total) {
+    const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (v >= m) return;
+    labels[v] = rank[root[v]];
+    if (v == m - 1) *total = rank[v] + flag[v];
+}
+
+// every sorted regular row: the label (and the root's code) of its distinct code
+__global__ void k_dir_rows(const uint32_t* __restrict__ row, const uint32_t* __restrict__ pos, int64_t n,
+                           const uint32_t* __restrict__ labels, const uint32_t* __restrict__ root,
+                           const uint64_t* __restrict__ D, uint32_t* __restrict__ cluster_id,
+                           uint64_t* __restrict__ root_code) {
+    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (k >= n) return;
+    const uint32_t j = pos[k] - 1u, i = row[k];
+    cluster_id[i] = labels[j];
+    if (root_code) root_code[i] = D[root[j]];
+}
+
+__global__ void k_dir_stats(int64_t* stats, int64_t n_regular_clusters) {
+    stats[0] = 0;
+    stats[1] = n_regular_clusters;
+}
+
+struct CodesLayout {
+    size_t off_ctrl, off_best, off_deg, off_flag, off_rank, off_adj, off_scan, scan_bytes, total;
+};
+
+int codes_layout(int64_t m, int L, CodesLayout* p) {
+    const int64_t m1 = std::max<int64_t>(m, 1);
+    size_t sb = 0;
+    ROGTK_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                                                     (int)m1));
+    size_t o = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = o;
+        o += al(bytes);
+        return at;
+    };
+    p->off_ctrl = take(kCtrlWords * 4);
+    p->off_best = take((size_t)m1 * 8);
+    p->off_deg = take((size_t)m1 * 4);
+    p->off_flag = take((size_t)m1 * 4);
+    p->off_rank = take((size_t)m1 * 4);
+    p->off_adj = take((size_t)m1 * 4 * (size_t)(3 * L));
+    p->scan_bytes = sb;
+    p->off_scan = take(sb);
+    p->total = o;
+    return ROGTK_OK;
+}
+
+struct Arena {
+    uint8_t* base = nullptr;
+    size_t off = 0;
+    hipStream_t s = nullptr;
+    ~Arena() {
+        if (base) (void)hipFreeAsync(base, s);
+    }
+    int get(size_t bytes, hipStream_t st) {
+        s = st;
+        ROGTK_HIP_CHECK(hipMallocAsync((void**)&base, std::max<size_t>(bytes, 256), st));
+        return ROGTK_OK;
+    }
+    template <class T>
+    T* take(int64_t count) {
+        uint8_t* p = base + off;
+        off += al((size_t)std::max<int64_t>(count, 1) * sizeof(T));
+        return (T*)p;
+    }
+};
+
+template <int OW, class K>
+int directional_column(const void* offs, const uint8_t* vals, const uint8_t* validity, int64_t voff, int64_t n, int L,
+                       uint32_t* cluster_id, uint64_t* root_code, int64_t* n_clusters, int64_t* rounds,
+                       int64_t* longest, hipStream_t s) {
+    const dim3 b(kBlock);
+    size_t sort_b = 0, scan_b = 0;
+    ROGTK_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_b, (const K*)nullptr, (K*)nullptr,
+                                                       (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0,
+                                                       L >= 1 && L <= 32 ? 2 * L : 2, s));
+    ROGTK_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(nullptr, scan_b, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                                                     (int)n, s));
+    const size_t tmp_b = std::max(sort_b, scan_b);
+    Arena A;
+    if (int rc = A.get(al(64) + 2 * al((size_t)n * sizeof(K)) + 4 * al((size_t)n * 4) + al((size_t)n * 8) +
+                           al(tmp_b) + 256,
+                       s))
+        return rc;
+    unsigned long long* cnt = A.take<unsigned long long>(8);
+    K* key = A.take<K>(n);
+    K* skey = A.take<K>(n);
+    uint32_t* row = A.take<uint32_t>(n);
+    uint32_t* srow = A.take<uint32_t>(n);
+    uint32_t* flag = A.take<uint32_t>(n);
+    uint32_t* pos = A.take<uint32_t>(n);
+    int64_t* irr = A.take<int64_t>(n);
+    void* tmp = A.take<uint8_t>((int64_t)tmp_b);
+    ROGTK_HIP_CHECK(hipMemsetAsync(cnt, 0, 64, s));
+    ROGTK_HIP_CHECK(hipMemsetAsync(cluster_id, 0xFF, (size_t)n * 4, s));
+    if (root_code) ROGTK_HIP_CHECK(hipMemsetAsync(root_code, 0xFF, (size_t)n * 8, s));
+    hipLaunchKernelGGL((k_dir_pack<OW, K>), dim3((unsigned)((n + kPackTile - 1) / kPackTile)), b, 0, s, offs, vals,
+                       validity, voff, n, L, key, row, irr, cnt);
+    ROGTK_HIP_CHECK(hipGetLastError());
+    unsigned long long h[3];
+    ROGTK_HIP_CHECK(hipMemcpyAsync(h, cnt, 24, hipMemcpyDeviceToHost, s));
+    ROGTK_HIP_CHECK(hipStreamSynchronize(s));
+    const int64_t n_reg = (int64_t)h[0], n_irr = (int64_t)h[1], max_len = (int64_t)h[2];
+    if (longest) *longest = std::max<int64_t>(max_len, n_reg > 0 ? L : 0);
+    int64_t n_reg_clusters = 0;
+    *rounds = 0;
+    if (n_reg > 0) {
+        const dim3 g(grid_for(n_reg));
+        size_t tb = tmp_b;
+        ROGTK_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key, skey, row, srow, (int)n_reg, 0, 2 * L, s));
+        hipLaunchKernelGGL(k_dir_heads<K>, g, b, 0, s, skey, n_reg, flag);
+        tb = tmp_b;
+        ROGTK_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(tmp, tb, flag, pos, (int)n_reg, s));
+        uint32_t m32 = 0;
+        ROGTK_HIP_CHECK(hipMemcpyAsync(&m32, pos + n_reg - 1, 4, hipMemcpyDeviceToHost, s));
+        ROGTK_HIP_CHECK(hipStreamSynchronize(s));
+        const int64_t m = (int64_t)m32;
+        int64_t codes_b = 0;
+        if (int rc = directional_codes_temp(m, L, &codes_b)) return rc;
+        Arena B;
+        if (int rc = B.get(al((size_t)m * 8) + 4 * al((size_t)m * 4) + al((size_t)codes_b) + 256, s)) return rc;
+        uint64_t* D = B.take<uint64_t>(m);
+        uint32_t* C = B.take<uint32_t>(m);
+        uint32_t* head = B.take<uint32_t>(m);
+        uint32_t* root = B.take<uint32_t>(m);
+        uint32_t* labels = B.take<uint32_t>(m);
+        void* ctemp = B.take<uint8_t>(codes_b);
+        hipLaunchKernelGGL(k_dir_distinct<K>, g, b, 0, s, skey, flag, pos, n_reg, D, head);
+        hipLaunchKernelGGL(k_dir_counts, dim3(grid_for(m)), b, 0, s, head, m, n_reg, C);
+        ROGTK_HIP_CHECK(hipGetLastError());
+        if (int rc = directional_codes(D, C, m, L, root, labels, &n_reg_clusters, rounds, ctemp, codes_b, s))
+            return rc;
+        hipLaunchKernelGGL(k_dir_rows, g, b, 0, s, srow, pos, n_reg, labels, root, D, cluster_id, root_code);
+        ROGTK_HIP_CHECK(hipGetLastError());
+    }
+    int64_t n_irr_clusters = 0;
+    if (n_irr > 0) {
+        int64_t* stats = (int64_t*)(cnt + 4);
+        hipLaunchKernelGGL(k_dir_stats, dim3(1), dim3(1), 0, s, stats, n_reg_clusters);
+        ROGTK_HIP_CHECK(hipGetLastError());
+        if (int rc = irregular_cluster(offs, OW, vals, irr, n_irr, max_len, stats, cluster_id, &n_irr_clusters, s))
+            return rc;
+    }
+    *n_clusters = n_reg_clusters + n_irr_clusters;
+    ROGTK_HIP_CHECK(hipStreamSynchronize(s));  // the arenas are released behind the last kernel
+    return ROGTK_OK;
+}
+
+}  // namespace
+
+int directional_codes_temp(int64_t m, int L, int64_t* bytes) {
+    CodesLayout p;
+    if (int rc = codes_layout(m, L, &p)) return rc;
+    *bytes = (int64_t)p.total;
+    return ROGTK_OK;
+}
+
+int directional_codes(const uint64_t* D, const uint32_t* C, int64_t m, int L, uint32_t* root, uint32_t* labels,
+                      int64_t* n_clusters, int64_t* rounds, void* temp, int64_t temp_bytes, hipStream_t s) {
+    *n_clusters = 0;
+    *rounds = 0;
+    if (m <= 0) return ROGTK_OK;
+    CodesLayout p;
+    if (int rc = codes_layout(m, L, &p)) return rc;
+    ROGTK_REQUIRE((int64_t)p.total <= temp_bytes, ROGTK_E_INVALID, "directional: temp_bytes %lld too small (need %lld)",
+                  (long long)temp_bytes, (long long)p.total);
+    uint8_t* t = (uint8_t*)temp;
+    uint32_t* ctrl = (uint32_t*)(t + p.off_ctrl);
+    unsigned long long* best = (unsigned long long*)(t + p.off_best);
+    uint32_t* deg = (uint32_t*)(t + p.off_deg);
+    uint32_t* flag = (uint32_t*)(t + p.off_flag);
+    uint32_t* rank = (uint32_t*)(t + p.off_rank);
+    uint32_t* adj = (uint32_t*)(t + p.off_adj);
+    const dim3 g(grid_for(m)), b(kBlock);
+    hipLaunchKernelGGL(k_dir_edges, g, b, 0, s, D, C, m, L, deg, adj, best);
+    ROGTK_HIP_CHECK(hipGetLastError());
+    auto launch = [&](int64_t, int k) -> int {
+        ROGTK_HIP_CHECK(hipMemsetAsync(ctrl, 0, 16, s));
+        for (int j = 0; j < k; ++j) hipLaunchKernelGGL(k_dir_relax, g, b, 0, s, deg, adj, m, best, ctrl + j);
+        ROGTK_HIP_CHECK(hipGetLastError());
+        return ROGTK_OK;
+    };
+    auto read = [&](int k, uint32_t* changed) -> int {
+        ROGTK_HIP_CHECK(hipMemcpyAsync(changed, ctrl, (size_t)k * 4, hipMemcpyDeviceToHost, s));
+        ROGTK_HIP_CHECK(hipStreamSynchronize(s));
+        return ROGTK_OK;
+    };
+    const int rc = directional_run_rounds(m, launch, read, rounds);
+    if (rc > 0) return rc;
+    ROGTK_REQUIRE(rc == 0, ROGTK_E_HIP, "directional: no fixed point after %lld rounds over %lld codes",
+                  (long long)*rounds, (long long)m);
+    hipLaunchKernelGGL(k_dir_roots, g, b, 0, s, best, m, root, flag);
+    size_t sb = p.scan_bytes;
+    ROGTK_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(t + p.off_scan, sb, flag, rank, (int)m, s));
+    hipLaunchKernelGGL(k_dir_labels, g, b, 0, s, root, flag, rank, m, labels, ctrl + 8);
+    ROGTK_HIP_CHECK(hipGetLastError());
+    uint32_t total = 0;
+    ROGTK_HIP_CHECK(hipMemcpyAsync(&total, ctrl + 8, 4, hipMemcpyDeviceToHost, s));
+    ROGTK_HIP_CHECK(hipStreamSynchronize(s));
+    *n_clusters = (int64_t)total;
+    return ROGTK_OK;
+}
+
+int directional_cluster(const void* offsets, int ow, const uint8_t* values, const uint8_t* validity, int64_t voff,
+                        int64_t n, int L, uint32_t* cluster_id, uint64_t* root_code, int64_t* n_clusters,
+                        int64_t* rounds, int64_t* longest, hipStream_t s) {
+    *n_clusters = 0;
+    *rounds = 0;
+    if (longest) *longest = 0;
+    if (n <= 0) return ROGTK_OK;
+    ROGTK_REQUIRE(n < (1ll << 31), ROGTK_E_UNSUPPORTED, "directional: at most 2^31 - 1 rows");
+    const bool wide = L > 16;
+    if (ow == 4)
+        return wide ? directional_column<4, uint64_t>(offsets, values, validity, voff, n, L, cluster_id, root_code,
+                                                      n_clusters, rounds, longest, s)
+                    : directional_column<4, uint32_t>(offsets, values, validity, voff, n, L, cluster_id, root_code,
+                                                      n_clusters, rounds, longest, s);
+    return wide ? directional_column<8, uint64_t>(offsets, values, validity, voff, n, L, cluster_id, root_code,
+                                                  n_clusters, rounds, longest, s)
+                : directional_column<8, uint32_t>(offsets, values, validity, voff, n, L, cluster_id, root_code,
+                                                  n_clusters, rounds, longest, s);
+}
+
+}  // namespace rogtk

@@ -1054,7 +1054,7 @@ void fuzzy_expr(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* o
 }
 
 // ------------------------------------------------------------ UMI correction
-// umi_correct_expr (no reference counterpart; DESIGN.md §4b): every chunk of the series as
+// umi_correct_expr (no reference counterpart; DESIGN.md §4b, §4c): every chunk of the series as
 // ONE batch (the clusters are global to the column) -> the corrected UMI of every row.
 struct U32ResultHolder {
     rogtk_u32_result r{};
@@ -1064,6 +1064,11 @@ void umi_correct_expr(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExp
     if (n_in < 1) fail("expected one input series");
     const int64_t umi_len = kw.opt_uint("umi_len", 0), maxd = kw.opt_uint("max_distance", 1);
     if (umi_len > (1 << 30) || maxd > (1 << 30)) fail("could not parse kwargs: umi_len / max_distance out of range");
+    std::string method = "cluster";  // "directional" = the count-aware rule
+    kw.opt_str("method", &method);
+    if (method != "cluster" && method != "directional")
+        fail("could not parse kwargs: unknown `method` \"%s\" (expected \"cluster\" or \"directional\")", method.c_str());
+    const bool directional = method == "directional";
     StrSeries s = str_series(in[0]);
     FlatCol f = flatten_all(s);
     const rogtk_str_col d = str_desc(f);
@@ -1071,8 +1076,9 @@ void umi_correct_expr(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExp
     StrResultHolder corrected, reps;
     U32ResultHolder n_reads, n_distinct;
     int64_t n_clusters = 0;
-    check(rogtk_umi_correct_host(&d, (int)umi_len, (int)maxd, ids.data(), &corrected.r, &reps.r, &n_reads.r,
-                                 &n_distinct.r, &n_clusters, nullptr));
+    check((directional ? rogtk_umi_correct_directional_host : rogtk_umi_correct_host)(
+        &d, (int)umi_len, (int)maxd, ids.data(), &corrected.r, &reps.r, &n_reads.r, &n_distinct.r, &n_clusters,
+        nullptr));
     std::vector<Col> chunks;
     chunks.push_back(view_col_result(corrected.r));
     export_series(out, {s.name, "vu", {}}, std::move(chunks));

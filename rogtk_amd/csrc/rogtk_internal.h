@@ -417,4 +417,19 @@ int corrected_fill(const void* offsets, int ow, const uint8_t* values, const uin
                    int64_t n, const uint32_t* ids, int64_t n_clusters, const int64_t* rep_row, uint8_t* out_values,
                    hipStream_t s);
 
+// ------------------------------------- directional UMI clustering (directional.hip)
+// D[m] ascending distinct codes, C[m] their row counts (device): root[m] (index into D),
+// labels[m] (dense, ascending in the root's code), *n_clusters and *rounds on the host.
+// Synchronises s. ROGTK_E_HIP when the relaxation has no fixed point after m rounds.
+int directional_codes_temp(int64_t m, int L, int64_t* bytes);
+int directional_codes(const uint64_t* D, const uint32_t* C, int64_t m, int L, uint32_t* root, uint32_t* labels,
+                      int64_t* n_clusters, int64_t* rounds, void* temp, int64_t temp_bytes, hipStream_t s);
+// a device string column: ids into cluster_id[n] (regular clusters, then the irregular strings
+// by exact bytes; 0xFFFFFFFF for null rows), root_code[n] (nullable: the code of the row's
+// root, all ones for a row that is not regular); *longest (nullable) = the byte length of the
+// longest non-null row. Synchronises s.
+int directional_cluster(const void* offsets, int ow, const uint8_t* values, const uint8_t* validity, int64_t voff,
+                        int64_t n, int L, uint32_t* cluster_id, uint64_t* root_code, int64_t* n_clusters,
+                        int64_t* rounds, int64_t* longest, hipStream_t s);
+
 }  // namespace rogtk

@@ -285,10 +285,10 @@ def register_polars():
         def dust_score(self):
             return reg("umi_dust_score_expr", self._expr, is_elementwise=True)
 
-        def correct(self, umi_len: int = 0, max_distance: int = 1):
+        def correct(self, umi_len: int = 0, max_distance: int = 1, method: str = "cluster"):
             # not elementwise: a row's corrected UMI depends on the whole column
-            return reg("umi_correct_expr", self._expr, {"umi_len": umi_len, "max_distance": max_distance},
-                       is_elementwise=False)
+            return reg("umi_correct_expr", self._expr,
+                       {"umi_len": umi_len, "max_distance": max_distance, "method": method}, is_elementwise=False)
 
     def umi_complexity_scores(expr):  # :493-526
         return reg("umi_complexity_all_expr", expr, is_elementwise=True)
