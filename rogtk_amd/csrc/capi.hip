@@ -519,21 +519,40 @@ __global__ void k_max_len(const O* __restrict__ off, int64_t n, unsigned long lo
     if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
 }
 
-// max_len of the column already uploaded to c->offsets (device reduction; one sync)
-int device_max_len(HostCtx* c, int ow, int64_t n, int64_t* out) {
-    if (int rc = c->nirr.ensure(16)) return rc;
-    unsigned long long* slot = c->nirr.as<unsigned long long>() + 1;
-    ROGTK_HIP_CHECK(hipMemsetAsync(slot, 0, 8, c->stream));
+// the longest row of a device column of n >= 1 rows, reduced into the zeroed device word `slot`
+int launch_max_len(const void* offsets, int ow, int64_t n, unsigned long long* slot, hipStream_t s) {
     const dim3 g((unsigned)((n + 255) / 256));
     if (ow == 4)
-        hipLaunchKernelGGL(k_max_len<int32_t>, g, dim3(256), 0, c->stream, c->offsets.as<int32_t>(), n, slot);
+        hipLaunchKernelGGL(k_max_len<int32_t>, g, dim3(256), 0, s, (const int32_t*)offsets, n, slot);
     else
-        hipLaunchKernelGGL(k_max_len<int64_t>, g, dim3(256), 0, c->stream, c->offsets.as<int64_t>(), n, slot);
+        hipLaunchKernelGGL(k_max_len<int64_t>, g, dim3(256), 0, s, (const int64_t*)offsets, n, slot);
     ROGTK_HIP_CHECK(hipGetLastError());
+    return ROGTK_OK;
+}
+
+// the same with the word zeroed first and read back: *out on the host (one sync of s)
+int column_max_len(const void* offsets, int ow, int64_t n, unsigned long long* slot, hipStream_t s, int64_t* out) {
+    ROGTK_HIP_CHECK(hipMemsetAsync(slot, 0, 8, s));
+    if (int rc = launch_max_len(offsets, ow, n, slot, s)) return rc;
     unsigned long long h = 0;
-    ROGTK_HIP_CHECK(hipMemcpyAsync(&h, slot, 8, hipMemcpyDeviceToHost, c->stream));
-    ROGTK_HIP_CHECK(hipStreamSynchronize(c->stream));
+    ROGTK_HIP_CHECK(hipMemcpyAsync(&h, slot, 8, hipMemcpyDeviceToHost, s));
+    ROGTK_HIP_CHECK(hipStreamSynchronize(s));
     *out = (int64_t)h;
+    return ROGTK_OK;
+}
+
+// the same for the column already uploaded to c->offsets
+int device_max_len(HostCtx* c, int ow, int64_t n, int64_t* out) {
+    if (int rc = c->nirr.ensure(16)) return rc;
+    return column_max_len(c->offsets.p, ow, n, c->nirr.as<unsigned long long>() + 1, c->stream, out);
+}
+
+// the size limits shared by the entries that take rows and cluster ids (an entry without a
+// cluster count passes 0)
+int check_rows_and_clusters(const char* name, int64_t n, int64_t n_clusters) {
+    ROGTK_REQUIRE(n >= 0 && n < (1ll << 31), ROGTK_E_UNSUPPORTED, "%s: n %lld outside 0..2^31-1", name, (long long)n);
+    ROGTK_REQUIRE(n_clusters >= 0 && n_clusters < (1ll << 32) - 1, ROGTK_E_INVALID, "%s: bad n_clusters %lld", name,
+                  (long long)n_clusters);
     return ROGTK_OK;
 }
 
@@ -1116,15 +1135,14 @@ static int cluster_dev(HostCtx* c, const int64_t* offsets, const uint8_t* values
         c->regbits.ensure((size_t)std::max<int64_t>(words, 1) * 8) != ROGTK_OK ||
         c->irr.ensure((size_t)std::max<int64_t>(n, 1) * 8) != ROGTK_OK || c->nirr.ensure(16) != ROGTK_OK)
         return ROGTK_E_HIP;
-    ROGTK_HIP_CHECK(hipMemsetAsync(c->nirr.p, 0, 16, s));
+    unsigned long long* cnt = c->nirr.as<unsigned long long>();  // [0] irregular rows, [1] the longest row
+    ROGTK_HIP_CHECK(hipMemsetAsync(cnt, 0, 16, s));
     if (int rc = launch_stage(offsets, 8, values, validity, 0, n, umi_len, c->codes.as<uint32_t>(),
-                              c->regbits.as<uint64_t>(), c->irr.as<int64_t>(), c->nirr.as<unsigned long long>(), s))
+                              c->regbits.as<uint64_t>(), c->irr.as<int64_t>(), cnt, s))
         return rc;
-    hipLaunchKernelGGL(k_max_len<int64_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, offsets, n,
-                       c->nirr.as<unsigned long long>() + 1);
-    ROGTK_HIP_CHECK(hipGetLastError());
-    int64_t hv[2];
-    ROGTK_HIP_CHECK(hipMemcpyAsync(hv, c->nirr.p, 16, hipMemcpyDeviceToHost, s));
+    if (int rc = launch_max_len(offsets, 8, n, cnt + 1, s)) return rc;
+    int64_t hv[2];  // both words in one read-back and one sync
+    ROGTK_HIP_CHECK(hipMemcpyAsync(hv, cnt, 16, hipMemcpyDeviceToHost, s));
     ROGTK_HIP_CHECK(hipStreamSynchronize(s));
     if (max_len) *max_len = hv[1];
     return cluster_staged(c, offsets, 8, values, validity, 0, n, umi_len, hv[0], hv[1], max_distance, cluster_id,
@@ -1155,10 +1173,7 @@ int rogtk_cluster_summary_temp_bytes(int64_t n, int umi_len, int64_t n_clusters,
     ROGTK_REQUIRE(bytes, ROGTK_E_INVALID, "cluster_summary_temp_bytes: NULL bytes");
     ROGTK_REQUIRE(umi_len >= 1 && umi_len <= kMaxPackedLen, ROGTK_E_UNSUPPORTED,
                   "packed cluster summary: umi_len %d outside 1..%d", umi_len, kMaxPackedLen);
-    ROGTK_REQUIRE(n >= 0 && n < (1ll << 31), ROGTK_E_UNSUPPORTED, "packed cluster summary: n %lld outside 0..2^31-1",
-                  (long long)n);
-    ROGTK_REQUIRE(n_clusters >= 0 && n_clusters < (1ll << 32) - 1, ROGTK_E_INVALID,
-                  "packed cluster summary: bad n_clusters %lld", (long long)n_clusters);
+    if (int rc = check_rows_and_clusters("packed cluster summary", n, n_clusters)) return rc;
     return cluster_summary_packed_temp(n, umi_len, n_clusters, bytes);
 }
 
@@ -1167,10 +1182,7 @@ int rogtk_cluster_summary_packed(const uint32_t* codes, const uint64_t* regular_
                                  uint32_t* n_distinct, void* temp, int64_t temp_bytes, void* stream) {
     ROGTK_REQUIRE(umi_len >= 1 && umi_len <= kMaxPackedLen, ROGTK_E_UNSUPPORTED,
                   "packed cluster summary: umi_len %d outside 1..%d", umi_len, kMaxPackedLen);
-    ROGTK_REQUIRE(n >= 0 && n < (1ll << 31), ROGTK_E_UNSUPPORTED, "packed cluster summary: n %lld outside 0..2^31-1",
-                  (long long)n);
-    ROGTK_REQUIRE(n_clusters >= 0 && n_clusters < (1ll << 32) - 1, ROGTK_E_INVALID,
-                  "packed cluster summary: bad n_clusters %lld", (long long)n_clusters);
+    if (int rc = check_rows_and_clusters("packed cluster summary", n, n_clusters)) return rc;
     ROGTK_REQUIRE(n == 0 || (codes && cluster_id), ROGTK_E_INVALID, "packed cluster summary: NULL codes / cluster_id");
     ROGTK_REQUIRE(n_clusters == 0 || (rep_code && n_reads && n_distinct), ROGTK_E_INVALID,
                   "packed cluster summary: NULL output table");
@@ -1404,10 +1416,7 @@ int rogtk_cluster_summary_dev(const int64_t* offsets, const uint8_t* values, con
                               int umi_len, const uint32_t* cluster_id, int64_t n_clusters, uint32_t* n_reads,
                               uint32_t* n_distinct, int64_t* rep_rows, int64_t* rep_offsets, int64_t* rep_values_len,
                               void* stream) {
-    ROGTK_REQUIRE(n >= 0 && n < (1ll << 31), ROGTK_E_UNSUPPORTED, "cluster_summary_dev: n %lld outside 0..2^31-1",
-                  (long long)n);
-    ROGTK_REQUIRE(n_clusters >= 0 && n_clusters < (1ll << 32) - 1, ROGTK_E_INVALID,
-                  "cluster_summary_dev: bad n_clusters %lld", (long long)n_clusters);
+    if (int rc = check_rows_and_clusters("cluster_summary_dev", n, n_clusters)) return rc;
     ROGTK_REQUIRE(n == 0 || (offsets && values && cluster_id), ROGTK_E_INVALID, "cluster_summary_dev: NULL input");
     ROGTK_REQUIRE(n_reads && n_distinct && rep_rows && rep_offsets && rep_values_len, ROGTK_E_INVALID,
                   "cluster_summary_dev: NULL output");
@@ -1419,12 +1428,7 @@ int rogtk_cluster_summary_dev(const int64_t* offsets, const uint8_t* values, con
     int64_t max_len = 0;
     if (n > 0) {
         if (int rc = c->nirr.ensure(16)) return rc;
-        unsigned long long* slot = c->nirr.as<unsigned long long>() + 1;
-        ROGTK_HIP_CHECK(hipMemsetAsync(slot, 0, 8, s));
-        hipLaunchKernelGGL(k_max_len<int64_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, offsets, n, slot);
-        ROGTK_HIP_CHECK(hipGetLastError());
-        ROGTK_HIP_CHECK(hipMemcpyAsync(&max_len, slot, 8, hipMemcpyDeviceToHost, s));
-        ROGTK_HIP_CHECK(hipStreamSynchronize(s));
+        if (int rc = column_max_len(offsets, 8, n, c->nirr.as<unsigned long long>() + 1, s, &max_len)) return rc;
     }
     if (int rc = cluster_summary_general(offsets, 8, values, validity, 0, n, umi_len, cluster_id, n_clusters, max_len,
                                          n_reads, n_distinct, rep_rows, s))
@@ -1447,11 +1451,27 @@ int rogtk_cluster_representatives_fill(const int64_t* offsets, const uint8_t* va
     return representatives_fill(offsets, 8, values, rep_rows, n_clusters, rep_offsets, rep_values, as_stream(stream));
 }
 
+namespace {
+// the tail of both *_correct*_dev entries: the per-cluster summary on the context's buffers,
+// then every row's bytes from its cluster's representative
+int correct_tail_dev(HostCtx* c, const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
+                     int umi_len, const uint32_t* cluster_id, int64_t nclu, int64_t max_len, uint8_t* corrected_values,
+                     hipStream_t s) {
+    const int64_t nc1 = std::max<int64_t>(nclu, 1);
+    if (c->out[1].ensure((size_t)nc1 * 4) || c->out[2].ensure((size_t)nc1 * 4) || c->out[3].ensure((size_t)nc1 * 8))
+        return ROGTK_E_HIP;
+    int64_t* rep_row = c->out[3].as<int64_t>();
+    if (int rc = cluster_summary_general(offsets, 8, values, validity, 0, n, umi_len, cluster_id, nclu, max_len,
+                                         c->out[1].as<uint32_t>(), c->out[2].as<uint32_t>(), rep_row, s))
+        return rc;
+    return corrected_fill(offsets, 8, values, validity, 0, n, cluster_id, nclu, rep_row, corrected_values, s);
+}
+}  // namespace
+
 int rogtk_umi_correct_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
                           int umi_len, int max_distance, uint32_t* cluster_id, int64_t* n_clusters,
                           uint8_t* corrected_values, void* stream) {
-    ROGTK_REQUIRE(n >= 0 && n < (1ll << 31), ROGTK_E_UNSUPPORTED, "umi_correct_dev: n %lld outside 0..2^31-1",
-                  (long long)n);
+    if (int rc = check_rows_and_clusters("umi_correct_dev", n, 0)) return rc;
     ROGTK_REQUIRE(n == 0 || (offsets && values && cluster_id && corrected_values), ROGTK_E_INVALID,
                   "umi_correct_dev: NULL argument");
     ROGTK_REQUIRE(umi_len >= 1, ROGTK_E_INVALID, "umi_correct_dev: umi_len must be >= 1");
@@ -1466,15 +1486,7 @@ int rogtk_umi_correct_dev(const int64_t* offsets, const uint8_t* values, const u
     if (int rc = cluster_dev(c, offsets, values, validity, n, umi_len, max_distance, cluster_id, &nclu, &max_len, s))
         return rc;
     if (n_clusters) *n_clusters = nclu;
-    const int64_t nc1 = std::max<int64_t>(nclu, 1);
-    if (c->out[1].ensure((size_t)nc1 * 4) || c->out[2].ensure((size_t)nc1 * 4) || c->out[3].ensure((size_t)nc1 * 8))
-        return ROGTK_E_HIP;
-    if (int rc = cluster_summary_general(offsets, 8, values, validity, 0, n, umi_len, cluster_id, nclu, max_len,
-                                         c->out[1].as<uint32_t>(), c->out[2].as<uint32_t>(), c->out[3].as<int64_t>(),
-                                         s))
-        return rc;
-    return corrected_fill(offsets, 8, values, validity, 0, n, cluster_id, nclu, c->out[3].as<int64_t>(),
-                          corrected_values, s);
+    return correct_tail_dev(c, offsets, values, validity, n, umi_len, cluster_id, nclu, max_len, corrected_values, s);
 }
 
 // ------------------------------------ directional UMI clustering (directional.hip)
@@ -1509,8 +1521,7 @@ int rogtk_directional_last_rounds(int64_t* rounds) {
 int rogtk_umi_cluster_directional_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
                                       int umi_len, uint32_t* cluster_id, int64_t* n_clusters, uint64_t* root_code,
                                       void* stream) {
-    ROGTK_REQUIRE(n >= 0 && n < (1ll << 31), ROGTK_E_UNSUPPORTED, "umi_cluster_directional_dev: n %lld outside 0..2^31-1",
-                  (long long)n);
+    if (int rc = check_rows_and_clusters("umi_cluster_directional_dev", n, 0)) return rc;
     ROGTK_REQUIRE(n == 0 || (offsets && values && cluster_id), ROGTK_E_INVALID,
                   "umi_cluster_directional_dev: NULL argument");
     ROGTK_REQUIRE(umi_len >= 1, ROGTK_E_INVALID, "umi_cluster_directional_dev: umi_len must be >= 1");
@@ -1528,8 +1539,7 @@ int rogtk_umi_cluster_directional_dev(const int64_t* offsets, const uint8_t* val
 int rogtk_umi_correct_directional_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
                                       int umi_len, uint32_t* cluster_id, int64_t* n_clusters,
                                       uint8_t* corrected_values, void* stream) {
-    ROGTK_REQUIRE(n >= 0 && n < (1ll << 31), ROGTK_E_UNSUPPORTED, "umi_correct_directional_dev: n %lld outside 0..2^31-1",
-                  (long long)n);
+    if (int rc = check_rows_and_clusters("umi_correct_directional_dev", n, 0)) return rc;
     ROGTK_REQUIRE(n == 0 || (offsets && values && cluster_id && corrected_values), ROGTK_E_INVALID,
                   "umi_correct_directional_dev: NULL argument");
     ROGTK_REQUIRE(umi_len >= 1, ROGTK_E_INVALID, "umi_correct_directional_dev: umi_len must be >= 1");
@@ -1544,15 +1554,7 @@ int rogtk_umi_correct_directional_dev(const int64_t* offsets, const uint8_t* val
                                      &t_directional_rounds, &max_len, s))
         return rc;
     if (n_clusters) *n_clusters = nclu;
-    const int64_t nc1 = std::max<int64_t>(nclu, 1);
-    if (c->out[1].ensure((size_t)nc1 * 4) || c->out[2].ensure((size_t)nc1 * 4) || c->out[3].ensure((size_t)nc1 * 8))
-        return ROGTK_E_HIP;
-    if (int rc = cluster_summary_general(offsets, 8, values, validity, 0, n, umi_len, cluster_id, nclu, max_len,
-                                         c->out[1].as<uint32_t>(), c->out[2].as<uint32_t>(), c->out[3].as<int64_t>(),
-                                         s))
-        return rc;
-    return corrected_fill(offsets, 8, values, validity, 0, n, cluster_id, nclu, c->out[3].as<int64_t>(),
-                          corrected_values, s);
+    return correct_tail_dev(c, offsets, values, validity, n, umi_len, cluster_id, nclu, max_len, corrected_values, s);
 }
 
 int rogtk_umi_cluster_directional_host(const void* offsets, int offset_width, const uint8_t* values, int64_t values_len,

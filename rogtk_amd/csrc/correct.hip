@@ -22,7 +22,7 @@
 
 #include <atomic>
 
-#include "rogtk_internal.h"
+#include "column_util.h"
 
 namespace rogtk {
 namespace {
@@ -32,8 +32,6 @@ constexpr int kTableMaxLen = 12;  // count-table method: 2 x 4^L x 4 bytes of te
 
 std::atomic<int> g_summary_method{0};  // 0 = sort, 1 = count table (L <= kTableMaxLen)
 
-inline size_t al(size_t b) { return (std::max<size_t>(b, 1) + 255) / 256 * 256; }
-inline unsigned grid_for(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + kBlock - 1) / kBlock); }
 
 __device__ __forceinline__ unsigned long long vote_key(uint64_t count, bool regular, uint32_t order) {
     return (count << 33) | ((uint64_t)regular << 32) | (uint64_t)(0xFFFFFFFFu - order);
@@ -288,25 +286,6 @@ int packed_layout(int64_t n, int L, int64_t n_clusters, PackedLayout* p) {
 }
 
 // ----------------------------------------------------------------- general
-template <int OW>
-__device__ __forceinline__ void span(const void* offs, int64_t row, int64_t& st, int64_t& len) {
-    if (OW == 4) {
-        const int32_t* o = (const int32_t*)offs;
-        st = o[row];
-        len = (int64_t)o[row + 1] - o[row];
-    } else {
-        const int64_t* o = (const int64_t*)offs;
-        st = o[row];
-        len = o[row + 1] - o[row];
-    }
-}
-
-__device__ __forceinline__ bool row_valid(const uint8_t* validity, int64_t voff, int64_t i) {
-    if (!validity) return true;
-    const int64_t b = voff + i;
-    return (validity[b >> 3] >> (b & 7)) & 1;
-}
-
 // the non-null rows, in any order (wave-aggregated append); flags an id >= n_clusters
 __global__ void k_valid_rows(const uint8_t* __restrict__ validity, int64_t voff, int64_t n,
                              const uint32_t* __restrict__ ids, int64_t n_clusters, int64_t* __restrict__ rows,
@@ -415,26 +394,6 @@ __global__ void k_corrected_fill(const void* __restrict__ offs, const uint8_t* _
     for (int64_t j = 0; j < len; ++j) out[st + j] = vals[rs + j];
 }
 
-struct Arena {
-    uint8_t* base = nullptr;
-    size_t off = 0;
-    hipStream_t s = nullptr;
-    ~Arena() {
-        if (base) (void)hipFreeAsync(base, s);
-    }
-    int get(size_t bytes, hipStream_t st) {
-        s = st;
-        ROGTK_HIP_CHECK(hipMallocAsync((void**)&base, std::max<size_t>(bytes, 256), st));
-        return ROGTK_OK;
-    }
-    template <class T>
-    T* take(int64_t count) {
-        uint8_t* p = base + off;
-        off += al((size_t)std::max<int64_t>(count, 1) * sizeof(T));
-        return (T*)p;
-    }
-};
-
 template <int OW>
 int summary_general(const void* offs, const uint8_t* vals, const uint8_t* validity, int64_t voff, int64_t n, int L,
                     const uint32_t* ids, int64_t n_clusters, int64_t max_len, uint32_t* n_reads,
@@ -462,8 +421,8 @@ int summary_general(const void* offs, const uint8_t* vals, const uint8_t* validi
     void* tmp = A.take<uint8_t>((int64_t)sort_b);
     ROGTK_HIP_CHECK(hipMemsetAsync(cnt, 0, 16, s));
     ROGTK_HIP_CHECK(hipMemsetAsync(votes, 0, (size_t)nc1 * 8, s));
-    hipLaunchKernelGGL(k_valid_rows, dim3(grid_for(n)), dim3(kBlock), 0, s, validity, voff, n, ids, n_clusters, rows,
-                       cnt);
+    hipLaunchKernelGGL(k_valid_rows, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, validity, voff, n, ids, n_clusters,
+                       rows, cnt);
     ROGTK_HIP_CHECK(hipGetLastError());
     unsigned long long h[2];
     ROGTK_HIP_CHECK(hipMemcpyAsync(h, cnt, 16, hipMemcpyDeviceToHost, s));
@@ -475,7 +434,7 @@ int summary_general(const void* offs, const uint8_t* vals, const uint8_t* validi
     // byte-lexicographic rank of every non-null row's string among the distinct strings
     int64_t n_strings = 0;
     if (int rc = irregular_cluster(offs, OW, vals, rows, m, max_len, nullptr, srank, &n_strings, s)) return rc;
-    const dim3 g(grid_for(m)), b(kBlock);
+    const dim3 g(grid_for(m, kBlock)), b(kBlock);
     hipLaunchKernelGGL(k_pair_keys, g, b, 0, s, rows, m, ids, srank, key, val);
     ROGTK_HIP_CHECK(hipGetLastError());
     size_t tb = sort_b;
@@ -523,8 +482,8 @@ int launch_cluster_summary_packed(const uint32_t* codes, const uint64_t* regbits
         uint32_t* tab = (uint32_t*)(t + p.off_tab);
         uint32_t* idtab = (uint32_t*)(t + p.off_idtab);
         ROGTK_HIP_CHECK(hipMemsetAsync(tab, 0, (size_t)space * 4, s));
-        hipLaunchKernelGGL(k_table_count, dim3(grid_for(n)), dim3(kBlock), 0, s, codes, regbits, ids, n, mask, tab,
-                           idtab);
+        hipLaunchKernelGGL(k_table_count, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, codes, regbits, ids, n, mask,
+                           tab, idtab);
         hipLaunchKernelGGL(k_table_vote, dim3(tiles_for(space)), dim3(kBlock), 0, s, tab, idtab, space, n_clusters,
                            VoteTables{votes, n_reads, n_distinct});
     } else if (n > 0 && n_clusters > 0) {
@@ -549,7 +508,8 @@ int launch_cluster_summary_packed(const uint32_t* codes, const uint64_t* regbits
                            VoteTables{votes, n_reads, n_distinct});
     }
     if (n_clusters > 0)
-        hipLaunchKernelGGL(k_rep_codes, dim3(grid_for(n_clusters)), dim3(kBlock), 0, s, votes, n_clusters, rep_code);
+        hipLaunchKernelGGL(k_rep_codes, dim3(grid_for(n_clusters, kBlock)), dim3(kBlock), 0, s, votes, n_clusters,
+                           rep_code);
     ROGTK_HIP_CHECK(hipGetLastError());
     return ROGTK_OK;
 }
@@ -560,9 +520,11 @@ int launch_cluster_correct_packed(const uint32_t* ids, const uint64_t* regbits, 
     const uint32_t nc = (uint32_t)std::min<int64_t>(n_clusters, 0xFFFFFFFFll);
     const bool vec = (((uintptr_t)ids | (uintptr_t)out) & 15u) == 0;
     const int64_t n4 = vec ? n / 4 : 0;
-    if (n4 > 0) hipLaunchKernelGGL(k_correct4, dim3(grid_for(n4)), dim3(kBlock), 0, s, ids, regbits, n4, rep_code, nc, out);
+    if (n4 > 0)
+        hipLaunchKernelGGL(k_correct4, dim3(grid_for(n4, kBlock)), dim3(kBlock), 0, s, ids, regbits, n4, rep_code, nc,
+                           out);
     if (4 * n4 < n)
-        hipLaunchKernelGGL(k_correct1, dim3(grid_for(n - 4 * n4)), dim3(kBlock), 0, s, ids, regbits, 4 * n4, n,
+        hipLaunchKernelGGL(k_correct1, dim3(grid_for(n - 4 * n4, kBlock)), dim3(kBlock), 0, s, ids, regbits, 4 * n4, n,
                            rep_code, nc, out);
     ROGTK_HIP_CHECK(hipGetLastError());
     return ROGTK_OK;
@@ -594,7 +556,7 @@ int representatives_measure(const void* offsets, int ow, const int64_t* rep_row,
     ROGTK_REQUIRE(temp && need <= temp_bytes, ROGTK_E_INVALID, "representatives: temp_bytes %lld too small (need %lld)",
                   (long long)temp_bytes, (long long)need);
     int64_t* lengths = (int64_t*)temp;
-    const dim3 g(grid_for(n_clusters + 1)), b(kBlock);
+    const dim3 g(grid_for(n_clusters + 1, kBlock)), b(kBlock);
     if (ow == 4) hipLaunchKernelGGL(k_rep_lengths<4>, g, b, 0, s, offsets, rep_row, n_clusters, lengths);
     else hipLaunchKernelGGL(k_rep_lengths<8>, g, b, 0, s, offsets, rep_row, n_clusters, lengths);
     ROGTK_HIP_CHECK(hipGetLastError());
@@ -608,7 +570,7 @@ int representatives_measure(const void* offsets, int ow, const int64_t* rep_row,
 int representatives_fill(const void* offsets, int ow, const uint8_t* values, const int64_t* rep_row, int64_t n_clusters,
                          const int64_t* out_offsets, uint8_t* out_values, hipStream_t s) {
     if (n_clusters <= 0) return ROGTK_OK;
-    const dim3 g(grid_for(n_clusters)), b(kBlock);
+    const dim3 g(grid_for(n_clusters, kBlock)), b(kBlock);
     if (ow == 4)
         hipLaunchKernelGGL(k_rep_fill<4>, g, b, 0, s, offsets, values, rep_row, n_clusters, out_offsets, out_values);
     else
@@ -621,7 +583,7 @@ int corrected_fill(const void* offsets, int ow, const uint8_t* values, const uin
                    int64_t n, const uint32_t* ids, int64_t n_clusters, const int64_t* rep_row, uint8_t* out_values,
                    hipStream_t s) {
     if (n <= 0) return ROGTK_OK;
-    const dim3 g(grid_for(n)), b(kBlock);
+    const dim3 g(grid_for(n, kBlock)), b(kBlock);
     if (ow == 4)
         hipLaunchKernelGGL(k_corrected_fill<4>, g, b, 0, s, offsets, values, validity, voff, n, ids, n_clusters,
                            rep_row, out_values);

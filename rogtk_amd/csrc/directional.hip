@@ -8,10 +8,9 @@
 // strings take no edges and are grouped by exact bytes (irregular.hip), after the regular
 // clusters.
 //
-//   count   the regular rows' (code, row) pairs, compacted and radix-sorted over the 2 L
-//           code bits (u32 keys for L <= 16, u64 above); heads of runs of equal codes,
-//           scanned, give the sorted distinct codes D[m], their counts C[m] and every
-//           sorted row's index into D.
+//   count   the shared front end (sorted_codes.hip): the regular rows sorted by code, the
+//           sorted distinct codes D[m], their counts C[m] and every sorted row's index
+//           into D.
 //   edges   one lane per distinct code v probes its 3 L one-substitution neighbours in D
 //           by binary search (two distinct integers d apart in value are at most d apart
 //           in a sorted array of distinct integers, which bounds the search window: the
@@ -28,136 +27,14 @@
 //   label   flag best[v] == key(v), scan in D order, labels[v] = rank of v's root.
 #include <hipcub/hipcub.hpp>
 
+#include "column_util.h"
 #include "directional_rounds.h"
-#include "rogtk_internal.h"
 
 namespace rogtk {
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kPackRows = 4;  // rows per thread of k_dir_pack
-constexpr int kPackTile = kBlock * kPackRows;
 constexpr int kCtrlWords = 64;  // [0, kDirBatch): changed words; [8]: cluster count
-
-inline size_t al(size_t b) { return (std::max<size_t>(b, 1) + 255) / 256 * 256; }
-inline unsigned grid_for(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + kBlock - 1) / kBlock); }
-
-template <int OW>
-__device__ __forceinline__ void span(const void* offs, int64_t row, int64_t& st, int64_t& len) {
-    if (OW == 4) {
-        const int32_t* o = (const int32_t*)offs;
-        st = o[row];
-        len = (int64_t)o[row + 1] - o[row];
-    } else {
-        const int64_t* o = (const int64_t*)offs;
-        st = o[row];
-        len = o[row + 1] - o[row];
-    }
-}
-
-__device__ __forceinline__ int base_code(uint8_t ch) {
-    return ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : -1;
-}
-
-// ------------------------------------------------------------------- count
-// Regular rows' (code, row) pairs appended to key / row, the irregular non-null rows to irr,
-// in any order (both are sorted later). A workgroup classifies kPackTile rows and reserves
-// its two ranges with one atomic each: cnt[0] regular rows, cnt[1] irregular rows; cnt[2] =
-// the longest irregular row.
-template <int OW, class K>
-__global__ void __launch_bounds__(kBlock)
-k_dir_pack(const void* __restrict__ offs, const uint8_t* __restrict__ vals, const uint8_t* __restrict__ validity,
-           int64_t voff, int64_t n, int L, K* __restrict__ key, uint32_t* __restrict__ row,
-           int64_t* __restrict__ irr, unsigned long long* __restrict__ cnt) {
-    constexpr int kWaves = kBlock / 64;
-    __shared__ uint32_t pre_r[kPackRows * kWaves], pre_i[kPackRows * kWaves];
-    __shared__ unsigned long long base[2];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t tile = (int64_t)blockIdx.x * kPackTile;
-    uint64_t code[kPackRows], rmask[kPackRows], imask[kPackRows];
-    unsigned long long longest = 0;
-    for (int r = 0; r < kPackRows; ++r) {
-        const int64_t i = tile + (int64_t)r * kBlock + threadIdx.x;
-        bool valid = false, regular = false;
-        uint64_t c = 0;
-        if (i < n) {
-            valid = true;
-            if (validity) {
-                const int64_t b = voff + i;
-                valid = (validity[b >> 3] >> (b & 7)) & 1;
-            }
-            if (valid) {
-                int64_t st, len;
-                span<OW>(offs, i, st, len);
-                regular = L >= 1 && L <= 32 && len == L;
-                for (int j = 0; regular && j < L; ++j) {
-                    const int b = base_code(vals[st + j]);
-                    regular = b >= 0;
-                    c = (c << 2) | (uint64_t)(b & 3);
-                }
-                if (!regular) longest = max(longest, (unsigned long long)len);
-            }
-        }
-        code[r] = c;
-        rmask[r] = __ballot(regular);
-        imask[r] = __ballot(valid && !regular);
-        if (lane == 0) {
-            pre_r[r * kWaves + wave] = (uint32_t)__popcll(rmask[r]);
-            pre_i[r * kWaves + wave] = (uint32_t)__popcll(imask[r]);
-        }
-    }
-    for (int d = 32; d; d >>= 1) longest = max(longest, (unsigned long long)__shfl_xor(longest, d));
-    if (lane == 0 && longest) atomicMax(&cnt[2], longest);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t sr = 0, si = 0;
-        for (int k = 0; k < kPackRows * kWaves; ++k) {
-            const uint32_t cr = pre_r[k], ci = pre_i[k];
-            pre_r[k] = sr;
-            pre_i[k] = si;
-            sr += cr;
-            si += ci;
-        }
-        base[0] = sr ? atomicAdd(&cnt[0], (unsigned long long)sr) : 0ull;
-        base[1] = si ? atomicAdd(&cnt[1], (unsigned long long)si) : 0ull;
-    }
-    __syncthreads();
-    const uint64_t below = (1ull << lane) - 1ull;
-    for (int r = 0; r < kPackRows; ++r) {
-        const int64_t i = tile + (int64_t)r * kBlock + threadIdx.x;
-        if ((rmask[r] >> lane) & 1ull) {
-            const int64_t p = (int64_t)base[0] + pre_r[r * kWaves + wave] + __popcll(rmask[r] & below);
-            key[p] = (K)code[r];
-            row[p] = (uint32_t)i;
-        } else if ((imask[r] >> lane) & 1ull) {
-            irr[(int64_t)base[1] + pre_i[r * kWaves + wave] + __popcll(imask[r] & below)] = i;
-        }
-    }
-}
-
-template <class K>
-__global__ void k_dir_heads(const K* __restrict__ key, int64_t n, uint32_t* __restrict__ flag) {
-    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (k >= n) return;
-    flag[k] = k == 0 || key[k - 1] != key[k];
-}
-
-// pos = inclusive scan of the head flags: the head of run j (pos j + 1) names D[j]
-template <class K>
-__global__ void k_dir_distinct(const K* __restrict__ key, const uint32_t* __restrict__ flag,
-                               const uint32_t* __restrict__ pos, int64_t n, uint64_t* __restrict__ D,
-                               uint32_t* __restrict__ head) {
-    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (k >= n || !flag[k]) return;
-    D[pos[k] - 1] = (uint64_t)key[k];
-    head[pos[k] - 1] = (uint32_t)k;
-}
-
-__global__ void k_dir_counts(const uint32_t* __restrict__ head, int64_t m, int64_t n, uint32_t* __restrict__ C) {
-    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (j >= m) return;
-    C[j] = (j + 1 < m ? head[j + 1] : (uint32_t)n) - head[j];
-}
 
 // ------------------------------------------------------------------- edges
 __device__ __forceinline__ unsigned long long dir_key(uint32_t count, uint32_t v) {
@@ -249,13 +126,13 @@ __global__ void k_dir_labels(const uint32_t* __restrict__ root, const uint32_t* 
 }
 
 // every sorted regular row: the label (and the root's code) of its distinct code
-__global__ void k_dir_rows(const uint32_t* __restrict__ row, const uint32_t* __restrict__ pos, int64_t n,
+__global__ void k_dir_rows(const uint32_t* __restrict__ row, const uint32_t* __restrict__ idx, int64_t n,
                            const uint32_t* __restrict__ labels, const uint32_t* __restrict__ root,
                            const uint64_t* __restrict__ D, uint32_t* __restrict__ cluster_id,
                            uint64_t* __restrict__ root_code) {
     const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (k >= n) return;
-    const uint32_t j = pos[k] - 1u, i = row[k];
+    const uint32_t j = idx[k], i = row[k];
     cluster_id[i] = labels[j];
     if (root_code) root_code[i] = D[root[j]];
 }
@@ -292,107 +169,6 @@ int codes_layout(int64_t m, int L, CodesLayout* p) {
     return ROGTK_OK;
 }
 
-struct Arena {
-    uint8_t* base = nullptr;
-    size_t off = 0;
-    hipStream_t s = nullptr;
-    ~Arena() {
-        if (base) (void)hipFreeAsync(base, s);
-    }
-    int get(size_t bytes, hipStream_t st) {
-        s = st;
-        ROGTK_HIP_CHECK(hipMallocAsync((void**)&base, std::max<size_t>(bytes, 256), st));
-        return ROGTK_OK;
-    }
-    template <class T>
-    T* take(int64_t count) {
-        uint8_t* p = base + off;
-        off += al((size_t)std::max<int64_t>(count, 1) * sizeof(T));
-        return (T*)p;
-    }
-};
-
-template <int OW, class K>
-int directional_column(const void* offs, const uint8_t* vals, const uint8_t* validity, int64_t voff, int64_t n, int L,
-                       uint32_t* cluster_id, uint64_t* root_code, int64_t* n_clusters, int64_t* rounds,
-                       int64_t* longest, hipStream_t s) {
-    const dim3 b(kBlock);
-    size_t sort_b = 0, scan_b = 0;
-    ROGTK_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_b, (const K*)nullptr, (K*)nullptr,
-                                                       (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0,
-                                                       L >= 1 && L <= 32 ? 2 * L : 2, s));
-    ROGTK_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(nullptr, scan_b, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                                     (int)n, s));
-    const size_t tmp_b = std::max(sort_b, scan_b);
-    Arena A;
-    if (int rc = A.get(al(64) + 2 * al((size_t)n * sizeof(K)) + 4 * al((size_t)n * 4) + al((size_t)n * 8) +
-                           al(tmp_b) + 256,
-                       s))
-        return rc;
-    unsigned long long* cnt = A.take<unsigned long long>(8);
-    K* key = A.take<K>(n);
-    K* skey = A.take<K>(n);
-    uint32_t* row = A.take<uint32_t>(n);
-    uint32_t* srow = A.take<uint32_t>(n);
-    uint32_t* flag = A.take<uint32_t>(n);
-    uint32_t* pos = A.take<uint32_t>(n);
-    int64_t* irr = A.take<int64_t>(n);
-    void* tmp = A.take<uint8_t>((int64_t)tmp_b);
-    ROGTK_HIP_CHECK(hipMemsetAsync(cnt, 0, 64, s));
-    ROGTK_HIP_CHECK(hipMemsetAsync(cluster_id, 0xFF, (size_t)n * 4, s));
-    if (root_code) ROGTK_HIP_CHECK(hipMemsetAsync(root_code, 0xFF, (size_t)n * 8, s));
-    hipLaunchKernelGGL((k_dir_pack<OW, K>), dim3((unsigned)((n + kPackTile - 1) / kPackTile)), b, 0, s, offs, vals,
-                       validity, voff, n, L, key, row, irr, cnt);
-    ROGTK_HIP_CHECK(hipGetLastError());
-    unsigned long long h[3];
-    ROGTK_HIP_CHECK(hipMemcpyAsync(h, cnt, 24, hipMemcpyDeviceToHost, s));
-    ROGTK_HIP_CHECK(hipStreamSynchronize(s));
-    const int64_t n_reg = (int64_t)h[0], n_irr = (int64_t)h[1], max_len = (int64_t)h[2];
-    if (longest) *longest = std::max<int64_t>(max_len, n_reg > 0 ? L : 0);
-    int64_t n_reg_clusters = 0;
-    *rounds = 0;
-    if (n_reg > 0) {
-        const dim3 g(grid_for(n_reg));
-        size_t tb = tmp_b;
-        ROGTK_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key, skey, row, srow, (int)n_reg, 0, 2 * L, s));
-        hipLaunchKernelGGL(k_dir_heads<K>, g, b, 0, s, skey, n_reg, flag);
-        tb = tmp_b;
-        ROGTK_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(tmp, tb, flag, pos, (int)n_reg, s));
-        uint32_t m32 = 0;
-        ROGTK_HIP_CHECK(hipMemcpyAsync(&m32, pos + n_reg - 1, 4, hipMemcpyDeviceToHost, s));
-        ROGTK_HIP_CHECK(hipStreamSynchronize(s));
-        const int64_t m = (int64_t)m32;
-        int64_t codes_b = 0;
-        if (int rc = directional_codes_temp(m, L, &codes_b)) return rc;
-        Arena B;
-        if (int rc = B.get(al((size_t)m * 8) + 4 * al((size_t)m * 4) + al((size_t)codes_b) + 256, s)) return rc;
-        uint64_t* D = B.take<uint64_t>(m);
-        uint32_t* C = B.take<uint32_t>(m);
-        uint32_t* head = B.take<uint32_t>(m);
-        uint32_t* root = B.take<uint32_t>(m);
-        uint32_t* labels = B.take<uint32_t>(m);
-        void* ctemp = B.take<uint8_t>(codes_b);
-        hipLaunchKernelGGL(k_dir_distinct<K>, g, b, 0, s, skey, flag, pos, n_reg, D, head);
-        hipLaunchKernelGGL(k_dir_counts, dim3(grid_for(m)), b, 0, s, head, m, n_reg, C);
-        ROGTK_HIP_CHECK(hipGetLastError());
-        if (int rc = directional_codes(D, C, m, L, root, labels, &n_reg_clusters, rounds, ctemp, codes_b, s))
-            return rc;
-        hipLaunchKernelGGL(k_dir_rows, g, b, 0, s, srow, pos, n_reg, labels, root, D, cluster_id, root_code);
-        ROGTK_HIP_CHECK(hipGetLastError());
-    }
-    int64_t n_irr_clusters = 0;
-    if (n_irr > 0) {
-        int64_t* stats = (int64_t*)(cnt + 4);
-        hipLaunchKernelGGL(k_dir_stats, dim3(1), dim3(1), 0, s, stats, n_reg_clusters);
-        ROGTK_HIP_CHECK(hipGetLastError());
-        if (int rc = irregular_cluster(offs, OW, vals, irr, n_irr, max_len, stats, cluster_id, &n_irr_clusters, s))
-            return rc;
-    }
-    *n_clusters = n_reg_clusters + n_irr_clusters;
-    ROGTK_HIP_CHECK(hipStreamSynchronize(s));  // the arenas are released behind the last kernel
-    return ROGTK_OK;
-}
-
 }  // namespace
 
 int directional_codes_temp(int64_t m, int L, int64_t* bytes) {
@@ -418,7 +194,7 @@ int directional_codes(const uint64_t* D, const uint32_t* C, int64_t m, int L, ui
     uint32_t* flag = (uint32_t*)(t + p.off_flag);
     uint32_t* rank = (uint32_t*)(t + p.off_rank);
     uint32_t* adj = (uint32_t*)(t + p.off_adj);
-    const dim3 g(grid_for(m)), b(kBlock);
+    const dim3 g(grid_for(m, kBlock)), b(kBlock);
     hipLaunchKernelGGL(k_dir_edges, g, b, 0, s, D, C, m, L, deg, adj, best);
     ROGTK_HIP_CHECK(hipGetLastError());
     auto launch = [&](int64_t, int k) -> int {
@@ -456,16 +232,41 @@ int directional_cluster(const void* offsets, int ow, const uint8_t* values, cons
     if (longest) *longest = 0;
     if (n <= 0) return ROGTK_OK;
     ROGTK_REQUIRE(n < (1ll << 31), ROGTK_E_UNSUPPORTED, "directional: at most 2^31 - 1 rows");
-    const bool wide = L > 16;
-    if (ow == 4)
-        return wide ? directional_column<4, uint64_t>(offsets, values, validity, voff, n, L, cluster_id, root_code,
-                                                      n_clusters, rounds, longest, s)
-                    : directional_column<4, uint32_t>(offsets, values, validity, voff, n, L, cluster_id, root_code,
-                                                      n_clusters, rounds, longest, s);
-    return wide ? directional_column<8, uint64_t>(offsets, values, validity, voff, n, L, cluster_id, root_code,
-                                                  n_clusters, rounds, longest, s)
-                : directional_column<8, uint32_t>(offsets, values, validity, voff, n, L, cluster_id, root_code,
-                                                  n_clusters, rounds, longest, s);
+    if (root_code) ROGTK_HIP_CHECK(hipMemsetAsync(root_code, 0xFF, (size_t)n * 8, s));
+    int64_t codes_b = 0;  // root, labels and the scratch of directional_codes ride in the front end's codes arena
+    const ExtraCodeBytes extra = [&](int64_t m, size_t* bytes) {
+        if (int rc = directional_codes_temp(m, L, &codes_b)) return rc;
+        *bytes = 2 * al((size_t)m * 4) + al((size_t)codes_b);
+        return (int)ROGTK_OK;
+    };
+    SortedCodes sc;
+    if (int rc = sorted_distinct_codes(offsets, ow, values, validity, voff, n, L, true, &extra, cluster_id, &sc, s))
+        return rc;
+    if (longest) *longest = std::max<int64_t>(sc.max_irr_len, sc.n_reg > 0 ? L : 0);
+    const int64_t m = sc.m;
+    int64_t* stats = sc.spare;
+    int64_t n_reg_clusters = 0;
+    if (sc.n_reg > 0) {
+        uint32_t* root = sc.codes_mem.take<uint32_t>(m);
+        uint32_t* labels = sc.codes_mem.take<uint32_t>(m);
+        void* ctemp = sc.codes_mem.take<uint8_t>(codes_b);
+        if (int rc = directional_codes(sc.D, sc.C, m, L, root, labels, &n_reg_clusters, rounds, ctemp, codes_b, s))
+            return rc;
+        hipLaunchKernelGGL(k_dir_rows, dim3(grid_for(sc.n_reg, kBlock)), dim3(kBlock), 0, s, sc.row, sc.idx, sc.n_reg,
+                           labels, root, sc.D, cluster_id, root_code);
+        ROGTK_HIP_CHECK(hipGetLastError());
+    }
+    int64_t n_irr_clusters = 0;
+    if (sc.n_irr > 0) {
+        hipLaunchKernelGGL(k_dir_stats, dim3(1), dim3(1), 0, s, stats, n_reg_clusters);
+        ROGTK_HIP_CHECK(hipGetLastError());
+        if (int rc = irregular_cluster(offsets, ow, values, sc.irr, sc.n_irr, sc.max_irr_len, stats, cluster_id,
+                                       &n_irr_clusters, s))
+            return rc;
+    }
+    *n_clusters = n_reg_clusters + n_irr_clusters;
+    ROGTK_HIP_CHECK(hipStreamSynchronize(s));  // the arenas are released behind the last kernel
+    return ROGTK_OK;
 }
 
 }  // namespace rogtk

@@ -18,7 +18,8 @@
 //                             indices into G -> all-gather the edges
 //   6. rogtk_cc_labels        hook-to-min + compress rounds over all edges on |G| vertices
 //                             (redundant on every rank, deterministic): dense labels in
-//                             order of each component's smallest code
+//                             order of each component's smallest code (cc_labels: also the
+//                             back end of long_cluster.hip and of irregular.hip's merge)
 //   7. rogtk_assign_codes     row -> its code's index in G (binary search) -> label
 //   8. rogtk_irregular_merge  irregular rows (all-gathered strings): exact-bytes groups, or
 //                             for max_distance 1 their Hamming-1 edges to each other and
@@ -27,48 +28,31 @@
 //   (7 runs after 8, so rows see the final labels)
 #include <hipcub/hipcub.hpp>
 
-#include <algorithm>
 #include <vector>
 
-#include "rogtk_internal.h"
+#include "column_util.h"
 
 namespace rogtk {
 namespace {
 
 constexpr int kB = 256;
 
-inline dim3 grid(int64_t n, int64_t cap = 1 << 20) {
-    return dim3((unsigned)std::min<int64_t>(cap, std::max<int64_t>(1, (n + kB - 1) / kB)));
-}
-
-__device__ __forceinline__ int base2(uint8_t c) {
-    return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1;
-}
+// every kernel here is grid-stride: at most 16384 workgroups
+inline dim3 grid(int64_t n) { return dim3(grid_for(n, kB, 16384)); }
 
 template <int OW>
 __global__ __launch_bounds__(kB) void k_long_codes(const void* __restrict__ offs, const uint8_t* __restrict__ vals,
                                                    const uint8_t* __restrict__ validity, int64_t voff, int64_t n, int L,
                                                    uint64_t* __restrict__ codes, uint8_t* __restrict__ kind) {
     for (int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x; i < n; i += (int64_t)gridDim.x * kB) {
-        bool valid = true;
-        if (validity) {
-            const int64_t b = voff + i;
-            valid = (validity[b >> 3] >> (b & 7)) & 1;
-        }
         uint64_t code = 0;
         uint8_t k = 0;
-        if (valid) {
+        if (row_valid(validity, voff, i)) {
             int64_t st, len;
-            if (OW == 4) {
-                st = ((const int32_t*)offs)[i];
-                len = (int64_t)((const int32_t*)offs)[i + 1] - st;
-            } else {
-                st = ((const int64_t*)offs)[i];
-                len = ((const int64_t*)offs)[i + 1] - st;
-            }
+            span<OW>(offs, i, st, len);
             bool regular = len == L;
             for (int j = 0; regular && j < L; ++j) {
-                const int b = base2(vals[st + j]);
+                const int b = base_code(vals[st + j]);
                 regular = b >= 0;
                 code = (code << 2) | (uint64_t)(b & 3);
             }
@@ -273,19 +257,6 @@ __global__ __launch_bounds__(kB) void k_assign_codes(const uint64_t* __restrict_
     }
 }
 
-struct Scratch {
-    void* p = nullptr;
-    hipStream_t s = nullptr;
-    ~Scratch() {
-        if (p) (void)hipFreeAsync(p, s);
-    }
-    int get(size_t bytes, hipStream_t st) {
-        s = st;
-        ROGTK_HIP_CHECK(hipMallocAsync(&p, std::max<size_t>(bytes, 256), st));
-        return ROGTK_OK;
-    }
-};
-
 int check_len(int L) {
     ROGTK_REQUIRE(L >= 1 && L <= 32, ROGTK_E_UNSUPPORTED, "sharded cluster: umi_len %d outside 1..32", L);
     return ROGTK_OK;
@@ -296,8 +267,48 @@ int check_len(int L) {
 int masked_records_range(const uint64_t* D, int64_t nd, int p0, int np, uint64_t* mk, uint32_t* pos, uint64_t* code,
                          hipStream_t s) {
     if (nd <= 0 || np <= 0) return ROGTK_OK;
-    hipLaunchKernelGGL(k_record_range, grid(nd * np, 16384), dim3(kB), 0, s, D, nd, p0, np, mk, pos, code);
+    hipLaunchKernelGGL(k_record_range, grid(nd * np), dim3(kB), 0, s, D, nd, p0, np, mk, pos, code);
     ROGTK_HIP_CHECK(hipGetLastError());
+    return ROGTK_OK;
+}
+
+int cc_labels(int64_t nv, const uint32_t* edges, int64_t m, uint32_t* labels, int64_t* n_clusters, hipStream_t s) {
+    *n_clusters = 0;
+    if (nv <= 0) return ROGTK_OK;
+    size_t scan_b = 0;
+    ROGTK_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)nv,
+                                                     s));
+    Arena S;
+    if (int rc = S.get(3 * al((size_t)nv * 4) + al(4) + al(scan_b), s)) return rc;
+    uint32_t* f = S.take<uint32_t>(nv);
+    uint32_t* rflag = S.take<uint32_t>(nv);
+    uint32_t* rlab = S.take<uint32_t>(nv);
+    unsigned int* changed = S.take<unsigned int>(1);
+    void* tmp = S.take<uint8_t>((int64_t)scan_b);
+    hipLaunchKernelGGL(k_iota, grid(nv), dim3(kB), 0, s, f, nv);
+    // hook-to-min + compress until no edge crosses two trees (f[x] <= x: roots are the
+    // components' smallest indices = smallest codes)
+    for (int round = 0; m > 0; ++round) {
+        ROGTK_REQUIRE(round < 4096, ROGTK_E_HIP, "cc_labels: rounds did not converge");
+        ROGTK_HIP_CHECK(hipMemsetAsync(changed, 0, 4, s));
+        hipLaunchKernelGGL(k_hook_edges, grid(m), dim3(kB), 0, s, (const uint2*)edges, m, f, changed);
+        hipLaunchKernelGGL(k_compress_all, grid(nv), dim3(kB), 0, s, f, nv);
+        ROGTK_HIP_CHECK(hipGetLastError());
+        unsigned int h = 0;
+        ROGTK_HIP_CHECK(hipMemcpyAsync(&h, changed, 4, hipMemcpyDeviceToHost, s));
+        ROGTK_HIP_CHECK(hipStreamSynchronize(s));
+        if (!h) break;
+    }
+    hipLaunchKernelGGL(k_root_flags, grid(nv), dim3(kB), 0, s, f, nv, rflag);
+    size_t b = scan_b;
+    ROGTK_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, b, rflag, rlab, (int)nv, s));
+    hipLaunchKernelGGL(k_labels, grid(nv), dim3(kB), 0, s, f, rlab, nv, labels);
+    ROGTK_HIP_CHECK(hipGetLastError());
+    uint32_t last[2];
+    ROGTK_HIP_CHECK(hipMemcpyAsync(&last[0], rlab + nv - 1, 4, hipMemcpyDeviceToHost, s));
+    ROGTK_HIP_CHECK(hipMemcpyAsync(&last[1], rflag + nv - 1, 4, hipMemcpyDeviceToHost, s));
+    ROGTK_HIP_CHECK(hipStreamSynchronize(s));
+    *n_clusters = (int64_t)last[0] + last[1];
     return ROGTK_OK;
 }
 
@@ -315,10 +326,10 @@ int rogtk_long_codes(const void* offsets, int offset_width, const uint8_t* value
     if (n == 0) return ROGTK_OK;
     hipStream_t s = (hipStream_t)stream;
     if (offset_width == 4)
-        hipLaunchKernelGGL(k_long_codes<4>, grid(n, 16384), dim3(kB), 0, s, offsets, values, validity,
+        hipLaunchKernelGGL(k_long_codes<4>, grid(n), dim3(kB), 0, s, offsets, values, validity,
                            validity_offset, n, umi_len, codes, kind);
     else
-        hipLaunchKernelGGL(k_long_codes<8>, grid(n, 16384), dim3(kB), 0, s, offsets, values, validity,
+        hipLaunchKernelGGL(k_long_codes<8>, grid(n), dim3(kB), 0, s, offsets, values, validity,
                            validity_offset, n, umi_len, codes, kind);
     ROGTK_HIP_CHECK(hipGetLastError());
     return ROGTK_OK;
@@ -340,18 +351,17 @@ int rogtk_unique_codes(const uint64_t* codes, const uint8_t* kind, int64_t n, in
     ROGTK_HIP_CHECK(hipcub::DeviceSelect::Unique(nullptr, uniq_b, (uint64_t*)nullptr, (uint64_t*)nullptr,
                                                  (int*)nullptr, (int)n, s));
     const size_t tb = std::max({sel_b, sort_b, uniq_b});
-    Scratch S;
-    const size_t a8 = ((size_t)n * 8 + 255) / 256 * 256, a1 = ((size_t)n + 255) / 256 * 256;
-    if (int rc = S.get(2 * a8 + a1 + 256 + tb, s)) return rc;
-    uint64_t* reg = (uint64_t*)S.p;
-    uint64_t* sorted = (uint64_t*)((uint8_t*)S.p + a8);
-    uint8_t* flags = (uint8_t*)S.p + 2 * a8;
-    int* cnt = (int*)((uint8_t*)S.p + 2 * a8 + a1);
-    void* tmp = (uint8_t*)S.p + 2 * a8 + a1 + 256;
+    Arena S;
+    if (int rc = S.get(2 * al((size_t)n * 8) + al((size_t)n) + al(4) + al(tb), s)) return rc;
+    uint64_t* reg = S.take<uint64_t>(n);
+    uint64_t* sorted = S.take<uint64_t>(n);
+    uint8_t* flags = S.take<uint8_t>(n);
+    int* cnt = S.take<int>(1);
+    void* tmp = S.take<uint8_t>((int64_t)tb);
     const uint64_t* src = codes;
     int nreg = (int)n;
     if (kind) {  // the regular rows' codes only
-        hipLaunchKernelGGL(k_regular_flags, grid(n, 16384), dim3(kB), 0, s, kind, n, flags);
+        hipLaunchKernelGGL(k_regular_flags, grid(n), dim3(kB), 0, s, kind, n, flags);
         size_t b = tb;
         ROGTK_HIP_CHECK(hipcub::DeviceSelect::Flagged(tmp, b, codes, flags, reg, cnt, (int)n, s));
         ROGTK_HIP_CHECK(hipMemcpyAsync(&nreg, cnt, 4, hipMemcpyDeviceToHost, s));
@@ -378,9 +388,9 @@ int rogtk_owner_counts(const uint64_t* sorted, int64_t n, int umi_len, int world
         for (int r = 0; r < world; ++r) counts[r] = 0;
         return ROGTK_OK;
     }
-    Scratch S;
-    if (int rc = S.get((size_t)(world + 1) * 8, s)) return rc;
-    int64_t* bounds = (int64_t*)S.p;
+    Arena S;
+    if (int rc = S.get(al((size_t)(world + 1) * 8), s)) return rc;
+    int64_t* bounds = S.take<int64_t>(world + 1);
     hipLaunchKernelGGL(k_owner_bounds, dim3((unsigned)((world + 1 + 255) / 256)), dim3(256), 0, s, sorted, n, umi_len,
                        world, bounds);
     ROGTK_HIP_CHECK(hipGetLastError());
@@ -402,11 +412,11 @@ int rogtk_masked_records(const uint64_t* D, int64_t n, int umi_len, int world, u
     ROGTK_REQUIRE(D && mk && pos && code, ROGTK_E_INVALID, "masked_records: NULL buffer");
     hipStream_t s = (hipStream_t)stream;
     if (world == 1) {  // one destination: records in (code, position) order, no packing sort
-        Scratch S1;
-        if (int rc = S1.get((size_t)total * 4, s)) return rc;
-        hipLaunchKernelGGL(k_iota, grid(total, 16384), dim3(kB), 0, s, (uint32_t*)S1.p, total);
-        hipLaunchKernelGGL(k_record_fill, grid(total, 16384), dim3(kB), 0, s, D, (const uint32_t*)S1.p, total,
-                           umi_len, mk, pos, code);
+        Arena S1;
+        if (int rc = S1.get(al((size_t)total * 4), s)) return rc;
+        uint32_t* rid = S1.take<uint32_t>(total);
+        hipLaunchKernelGGL(k_iota, grid(total), dim3(kB), 0, s, rid, total);
+        hipLaunchKernelGGL(k_record_fill, grid(total), dim3(kB), 0, s, D, rid, total, umi_len, mk, pos, code);
         ROGTK_HIP_CHECK(hipGetLastError());
         counts[0] = total;
         return ROGTK_OK;
@@ -414,21 +424,20 @@ int rogtk_masked_records(const uint64_t* D, int64_t n, int umi_len, int world, u
     size_t sort_b = 0;
     ROGTK_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_b, (uint32_t*)nullptr, (uint32_t*)nullptr,
                                                        (uint32_t*)nullptr, (uint32_t*)nullptr, (int)total, 0, 32, s));
-    const size_t a4 = ((size_t)total * 4 + 255) / 256 * 256;
-    Scratch S;
-    if (int rc = S.get(4 * a4 + (size_t)world * 8 + 256 + sort_b, s)) return rc;
-    uint32_t* dest = (uint32_t*)S.p;
-    uint32_t* rid = (uint32_t*)((uint8_t*)S.p + a4);
-    uint32_t* sdest = (uint32_t*)((uint8_t*)S.p + 2 * a4);
-    uint32_t* srid = (uint32_t*)((uint8_t*)S.p + 3 * a4);
-    int64_t* dcnt = (int64_t*)((uint8_t*)S.p + 4 * a4);
-    void* tmp = (uint8_t*)S.p + 4 * a4 + (size_t)world * 8 + 256;
-    hipLaunchKernelGGL(k_record_dest, grid(total, 16384), dim3(kB), 0, s, D, n, umi_len, world, dest, rid);
+    Arena S;
+    if (int rc = S.get(4 * al((size_t)total * 4) + al((size_t)world * 8) + al(sort_b), s)) return rc;
+    uint32_t* dest = S.take<uint32_t>(total);
+    uint32_t* rid = S.take<uint32_t>(total);
+    uint32_t* sdest = S.take<uint32_t>(total);
+    uint32_t* srid = S.take<uint32_t>(total);
+    int64_t* dcnt = S.take<int64_t>(world);
+    void* tmp = S.take<uint8_t>((int64_t)sort_b);
+    hipLaunchKernelGGL(k_record_dest, grid(total), dim3(kB), 0, s, D, n, umi_len, world, dest, rid);
     int dbits = 1;
     while ((1 << dbits) < world) ++dbits;
     size_t b = sort_b;
     ROGTK_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, b, dest, sdest, rid, srid, (int)total, 0, dbits, s));
-    hipLaunchKernelGGL(k_record_fill, grid(total, 16384), dim3(kB), 0, s, D, srid, total, umi_len, mk, pos, code);
+    hipLaunchKernelGGL(k_record_fill, grid(total), dim3(kB), 0, s, D, srid, total, umi_len, mk, pos, code);
     hipLaunchKernelGGL(k_dest_counts, dim3((unsigned)((world + 255) / 256)), dim3(256), 0, s, sdest, total, world, dcnt);
     ROGTK_HIP_CHECK(hipGetLastError());
     ROGTK_HIP_CHECK(hipMemcpyAsync(counts, dcnt, (size_t)world * 8, hipMemcpyDeviceToHost, s));
@@ -450,26 +459,25 @@ int rogtk_clique_edges(const uint64_t* mk, const uint32_t* pos, const uint64_t* 
     ROGTK_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, b2, (uint32_t*)nullptr, (uint32_t*)nullptr,
                                                        (uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 8, s));
     const size_t tb = std::max(b1, b2);
-    const size_t a8 = ((size_t)n * 8 + 255) / 256 * 256, a4 = ((size_t)n * 4 + 255) / 256 * 256;
-    Scratch S;
-    if (int rc = S.get(a8 + 5 * a4 + 256 + tb, s)) return rc;
-    uint64_t* smk = (uint64_t*)S.p;
-    uint32_t* idx = (uint32_t*)((uint8_t*)S.p + a8);
-    uint32_t* perm1 = (uint32_t*)((uint8_t*)S.p + a8 + a4);
-    uint32_t* p1 = (uint32_t*)((uint8_t*)S.p + a8 + 2 * a4);
-    uint32_t* sp = (uint32_t*)((uint8_t*)S.p + a8 + 3 * a4);
-    uint32_t* perm = (uint32_t*)((uint8_t*)S.p + a8 + 4 * a4);
-    unsigned long long* ne = (unsigned long long*)((uint8_t*)S.p + a8 + 5 * a4);
-    void* tmp = (uint8_t*)S.p + a8 + 5 * a4 + 256;
+    Arena S;
+    if (int rc = S.get(al((size_t)n * 8) + 5 * al((size_t)n * 4) + al(8) + al(tb), s)) return rc;
+    uint64_t* smk = S.take<uint64_t>(n);
+    uint32_t* idx = S.take<uint32_t>(n);
+    uint32_t* perm1 = S.take<uint32_t>(n);
+    uint32_t* p1 = S.take<uint32_t>(n);
+    uint32_t* sp = S.take<uint32_t>(n);
+    uint32_t* perm = S.take<uint32_t>(n);
+    unsigned long long* ne = S.take<unsigned long long>(1);
+    void* tmp = S.take<uint8_t>((int64_t)tb);
     // LSD order: by masked key, then stably by position -> groups contiguous by (p, key)
-    hipLaunchKernelGGL(k_iota, grid(n, 16384), dim3(kB), 0, s, idx, n);
+    hipLaunchKernelGGL(k_iota, grid(n), dim3(kB), 0, s, idx, n);
     size_t b = tb;
     ROGTK_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, b, mk, smk, idx, perm1, (int)n, 0, 2 * umi_len, s));
-    hipLaunchKernelGGL(k_gather_pos, grid(n, 16384), dim3(kB), 0, s, pos, perm1, n, p1);
+    hipLaunchKernelGGL(k_gather_pos, grid(n), dim3(kB), 0, s, pos, perm1, n, p1);
     b = tb;
     ROGTK_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, b, p1, sp, perm1, perm, (int)n, 0, 8, s));
     ROGTK_HIP_CHECK(hipMemsetAsync(ne, 0, 8, s));
-    hipLaunchKernelGGL(k_group_edges, grid(n, 16384), dim3(kB), 0, s, mk, pos, code, perm, n, G, ng, (uint2*)edges, ne);
+    hipLaunchKernelGGL(k_group_edges, grid(n), dim3(kB), 0, s, mk, pos, code, perm, n, G, ng, (uint2*)edges, ne);
     ROGTK_HIP_CHECK(hipGetLastError());
     unsigned long long h = 0;
     ROGTK_HIP_CHECK(hipMemcpyAsync(&h, ne, 8, hipMemcpyDeviceToHost, s));
@@ -484,43 +492,7 @@ int rogtk_cc_labels(int64_t nv, const uint32_t* edges, int64_t m, uint32_t* labe
     *n_clusters = 0;
     if (nv == 0) return ROGTK_OK;
     ROGTK_REQUIRE(labels && (m == 0 || edges), ROGTK_E_INVALID, "cc_labels: NULL buffer");
-    hipStream_t s = (hipStream_t)stream;
-    size_t scan_b = 0;
-    ROGTK_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)nv,
-                                                     s));
-    const size_t a4 = ((size_t)nv * 4 + 255) / 256 * 256;
-    Scratch S;
-    if (int rc = S.get(3 * a4 + 256 + scan_b, s)) return rc;
-    uint32_t* f = (uint32_t*)S.p;
-    uint32_t* rflag = (uint32_t*)((uint8_t*)S.p + a4);
-    uint32_t* rlab = (uint32_t*)((uint8_t*)S.p + 2 * a4);
-    unsigned int* changed = (unsigned int*)((uint8_t*)S.p + 3 * a4);
-    void* tmp = (uint8_t*)S.p + 3 * a4 + 256;
-    hipLaunchKernelGGL(k_iota, grid(nv, 16384), dim3(kB), 0, s, f, nv);
-    // hook-to-min + compress until no edge crosses two trees (f[x] <= x: roots are the
-    // components' smallest indices = smallest codes)
-    for (int round = 0; m > 0; ++round) {
-        ROGTK_REQUIRE(round < 4096, ROGTK_E_HIP, "cc_labels: rounds did not converge");
-        ROGTK_HIP_CHECK(hipMemsetAsync(changed, 0, 4, s));
-        hipLaunchKernelGGL(k_hook_edges, grid(m, 16384), dim3(kB), 0, s, (const uint2*)edges, m, f, changed);
-        hipLaunchKernelGGL(k_compress_all, grid(nv, 16384), dim3(kB), 0, s, f, nv);
-        ROGTK_HIP_CHECK(hipGetLastError());
-        unsigned int h = 0;
-        ROGTK_HIP_CHECK(hipMemcpyAsync(&h, changed, 4, hipMemcpyDeviceToHost, s));
-        ROGTK_HIP_CHECK(hipStreamSynchronize(s));
-        if (!h) break;
-    }
-    hipLaunchKernelGGL(k_root_flags, grid(nv, 16384), dim3(kB), 0, s, f, nv, rflag);
-    size_t b = scan_b;
-    ROGTK_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, b, rflag, rlab, (int)nv, s));
-    hipLaunchKernelGGL(k_labels, grid(nv, 16384), dim3(kB), 0, s, f, rlab, nv, labels);
-    ROGTK_HIP_CHECK(hipGetLastError());
-    uint32_t last[2];
-    ROGTK_HIP_CHECK(hipMemcpyAsync(&last[0], rlab + nv - 1, 4, hipMemcpyDeviceToHost, s));
-    ROGTK_HIP_CHECK(hipMemcpyAsync(&last[1], rflag + nv - 1, 4, hipMemcpyDeviceToHost, s));
-    ROGTK_HIP_CHECK(hipStreamSynchronize(s));
-    *n_clusters = (int64_t)last[0] + last[1];
-    return ROGTK_OK;
+    return cc_labels(nv, edges, m, labels, n_clusters, (hipStream_t)stream);
 }
 
 int rogtk_assign_codes(const uint64_t* codes, const uint8_t* kind, int64_t n, const uint64_t* G, int64_t ng,
@@ -530,11 +502,11 @@ int rogtk_assign_codes(const uint64_t* codes, const uint8_t* kind, int64_t n, co
     ROGTK_REQUIRE(codes && kind && cluster_id && (ng == 0 || (G && labels)), ROGTK_E_INVALID,
                   "assign_codes: NULL buffer");
     hipStream_t s = (hipStream_t)stream;
-    Scratch S;
-    if (int rc = S.get(256, s)) return rc;
-    unsigned int* missing = (unsigned int*)S.p;
+    Arena S;
+    if (int rc = S.get(al(4), s)) return rc;
+    unsigned int* missing = S.take<unsigned int>(1);
     ROGTK_HIP_CHECK(hipMemsetAsync(missing, 0, 4, s));
-    hipLaunchKernelGGL(k_assign_codes, grid(n, 16384), dim3(kB), 0, s, codes, kind, n, G, ng, labels, cluster_id,
+    hipLaunchKernelGGL(k_assign_codes, grid(n), dim3(kB), 0, s, codes, kind, n, G, ng, labels, cluster_id,
                        missing);
     ROGTK_HIP_CHECK(hipGetLastError());
     unsigned int h = 0;
@@ -551,11 +523,10 @@ int rogtk_group_strings(const int64_t* offsets, const uint8_t* values, int64_t n
     if (n == 0) return ROGTK_OK;
     ROGTK_REQUIRE(offsets && ids, ROGTK_E_INVALID, "group_strings: NULL buffer");
     hipStream_t s = (hipStream_t)stream;
-    Scratch S;
-    const size_t a8 = ((size_t)n * 8 + 255) / 256 * 256;
-    if (int rc = S.get(a8 + 256, s)) return rc;
-    int64_t* rows = (int64_t*)S.p;
-    int64_t* base = (int64_t*)((uint8_t*)S.p + a8);  // stats block: [1] = the id base
+    Arena S;
+    if (int rc = S.get(al((size_t)n * 8) + al(16), s)) return rc;
+    int64_t* rows = S.take<int64_t>(n);
+    int64_t* base = S.take<int64_t>(2);  // stats block: [1] = the id base
     std::vector<int64_t> hrows((size_t)n);
     for (int64_t i = 0; i < n; ++i) hrows[(size_t)i] = i;
     const int64_t hb[2] = {0, (int64_t)id_base};
@@ -586,10 +557,10 @@ int rogtk_irregular_merge(const int64_t* offsets, const uint8_t* values, int64_t
     }
     ROGTK_REQUIRE(offsets && ids && (ng == 0 || (G && labels)), ROGTK_E_INVALID, "irregular_merge: NULL buffer");
     hipStream_t s = (hipStream_t)stream;
-    Scratch S;
-    if (int rc = S.get((size_t)n * 8, s)) return rc;
-    int64_t* rows = (int64_t*)S.p;
-    hipLaunchKernelGGL(k_iota64, grid(n, 16384), dim3(kB), 0, s, rows, n);
+    Arena S;
+    if (int rc = S.get(al((size_t)n * 8), s)) return rc;
+    int64_t* rows = S.take<int64_t>(n);
+    hipLaunchKernelGGL(k_iota64, grid(n), dim3(kB), 0, s, rows, n);
     ROGTK_HIP_CHECK(hipGetLastError());
     CodeLookup lk = [&](const uint64_t* q, int64_t nq, uint32_t* lab, hipStream_t st) {
         return sorted_code_lookup(G, ng, labels, q, nq, lab, st);

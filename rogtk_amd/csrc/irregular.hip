@@ -31,7 +31,7 @@
 // are found by comparing bytes; a flag + scan numbers the distinct strings.
 #include <hipcub/hipcub.hpp>
 
-#include "rogtk_internal.h"
+#include "column_util.h"
 
 namespace rogtk {
 namespace {
@@ -40,19 +40,6 @@ constexpr int kBlock = 256;
 constexpr uint32_t kNoLabel = 0xFFFFFFFFu;
 constexpr uint64_t kNoCode = ~0ull;
 constexpr int kMaxRunWalk = 4096;  // masked-key run members compared per record (bytes decide)
-
-template <int OW>
-__device__ __forceinline__ void span(const void* offs, int64_t row, int64_t& st, int64_t& len) {
-    if (OW == 4) {
-        const int32_t* o = (const int32_t*)offs;
-        st = o[row];
-        len = (int64_t)o[row + 1] - o[row];
-    } else {
-        const int64_t* o = (const int64_t*)offs;
-        st = o[row];
-        len = o[row + 1] - o[row];
-    }
-}
 
 template <int OW>
 __global__ void k_len_keys(const void* __restrict__ offs, const int64_t* __restrict__ rows, int64_t n,
@@ -124,10 +111,6 @@ __device__ __forceinline__ uint64_t fmix64(uint64_t h) {
 // per-position multiplier of the string hash h = sum_i b_i * R(i) (mod 2^64)
 __device__ __forceinline__ uint64_t pos_mult(int64_t i) { return fmix64((uint64_t)i + 0x9E3779B97F4A7C15ull) | 1ull; }
 
-__device__ __forceinline__ int base2(uint8_t c) {
-    return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1;
-}
-
 // distinct string d (sorted order) -> its first row and length
 template <int OW>
 __global__ void k_distinct_rep(const void* __restrict__ offs, const int64_t* __restrict__ rows,
@@ -168,7 +151,7 @@ __global__ void k_records(const void* __restrict__ offs, const uint8_t* __restri
         int bad = -1, nbad = 0;
         if (L >= 1 && L <= 32 && len == L) {
             for (int i = 0; i < L; ++i) {
-                int b = base2(s[i]);
+                int b = base_code(s[i]);
                 if (b < 0) {
                     ++nbad;
                     bad = i;
@@ -297,31 +280,6 @@ __global__ void k_sorted_lookup(const uint64_t* __restrict__ G, int64_t ng, cons
     }
 }
 
-inline int grid_for(int64_t n, int64_t cap = 1 << 20) {
-    return (int)std::min<int64_t>(cap, std::max<int64_t>(1, (n + kBlock - 1) / kBlock));
-}
-
-struct Arena {
-    uint8_t* base = nullptr;
-    size_t off = 0;
-    hipStream_t s = nullptr;
-    ~Arena() {
-        if (base) (void)hipFreeAsync(base, s);
-    }
-    int get(size_t bytes, hipStream_t st) {
-        s = st;
-        ROGTK_HIP_CHECK(hipMallocAsync((void**)&base, std::max<size_t>(bytes, 256), st));
-        return ROGTK_OK;
-    }
-    template <class T>
-    T* take(int64_t count) {
-        uint8_t* p = base + off;
-        off += ((size_t)std::max<int64_t>(count, 1) * sizeof(T) + 255) / 256 * 256;
-        return (T*)p;
-    }
-};
-inline size_t al(size_t b) { return (std::max<size_t>(b, 1) + 255) / 256 * 256; }
-
 // The sorted order of the irregular rows: perm (sorted position -> index into rows),
 // flag (first copy of a string), rank (exclusive scan of flag = distinct index - [!flag]).
 struct StringSort {
@@ -349,7 +307,7 @@ int sort_strings(const void* offs, const uint8_t* vals, const int64_t* rows, int
     uint32_t* flag = S.A.take<uint32_t>(n);
     uint32_t* rank = S.A.take<uint32_t>(n);
     void* tmp = S.A.take<uint8_t>((int64_t)tmp_bytes);
-    const dim3 g(grid_for(n, 1ll << 31)), b(kBlock);
+    const dim3 g(grid_for(n, kBlock)), b(kBlock);
     auto sort = [&]() -> int {
         size_t tb = tmp_bytes;
         ROGTK_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key, key2, perm, perm2, (int)n, 0, 64, s));
@@ -384,7 +342,7 @@ int run_exact(const void* offs, const uint8_t* vals, const int64_t* rows, int64_
     if (int rc = sort_strings<OW>(offs, vals, rows, n, max_len, S, s)) return rc;
     Arena M;
     if (int rc = M.get(256, s)) return rc;
-    hipLaunchKernelGGL(k_irr_assign, dim3(grid_for(n, 1ll << 31)), dim3(kBlock), 0, s, rows, S.perm, S.rank, S.flag,
+    hipLaunchKernelGGL(k_irr_assign, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, rows, S.perm, S.rank, S.flag,
                        n, stats_dev, cluster_id, M.take<uint32_t>(1));
     ROGTK_HIP_CHECK(hipGetLastError());
     ROGTK_HIP_CHECK(hipStreamSynchronize(s));
@@ -412,7 +370,7 @@ int run_merge(const void* offs, const uint8_t* vals, const int64_t* rows, int64_
     void* stmp = D.take<uint8_t>((int64_t)scan_b);
     ROGTK_HIP_CHECK(hipMemsetAsync(dlen + nd, 0, 8, s));
     ROGTK_HIP_CHECK(hipMemsetAsync(cnt, 0, 32, s));
-    hipLaunchKernelGGL(k_distinct_rep<OW>, dim3(grid_for(n, 1ll << 31)), dim3(kBlock), 0, s, offs, rows, S.perm,
+    hipLaunchKernelGGL(k_distinct_rep<OW>, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, offs, rows, S.perm,
                        S.rank, S.flag, n, rep, dlen);
     size_t tb = scan_b;
     ROGTK_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(stmp, tb, dlen, roff, (int)(nd + 1), s));
@@ -442,19 +400,20 @@ int run_merge(const void* offs, const uint8_t* vals, const int64_t* rows, int64_
     uint32_t* lab4 = want_regular ? R.take<uint32_t>(4 * nd) : nullptr;
     uint32_t* labels = R.take<uint32_t>(n_reg + nd);
     const uint32_t vbase = (uint32_t)n_reg;
-    hipLaunchKernelGGL(k_records<OW>, dim3(grid_for(nd, 1ll << 31)), dim3(kBlock), 0, s, offs, vals, rep, roff, nd, L,
+    hipLaunchKernelGGL(k_records<OW>, dim3(grid_for(nd, kBlock)), dim3(kBlock), 0, s, offs, vals, rep, roff, nd, L,
                        key, val, q);
     ROGTK_HIP_CHECK(hipGetLastError());
     if (nr > 1) {
         size_t b = sort_b;
         ROGTK_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, b, key, skey, val, sval, (int)nr, 0, 64, s));
-        hipLaunchKernelGGL(k_masked_edges<OW>, dim3(grid_for(nr, 16384)), dim3(kBlock), 0, s, offs, vals, rep, skey,
-                           sval, nr, vbase, E, cnt, (unsigned int*)(cnt + 1));
+        hipLaunchKernelGGL(k_masked_edges<OW>, dim3(grid_for(nr, kBlock, 16384)), dim3(kBlock), 0, s, offs, vals, rep,
+                           skey, sval, nr, vbase, E, cnt, (unsigned int*)(cnt + 1));
         ROGTK_HIP_CHECK(hipGetLastError());
     }
     if (want_regular) {
         if (int rc = (*lookup)(q, 4 * nd, lab4, s)) return rc;
-        hipLaunchKernelGGL(k_regular_edges, dim3(grid_for(nd, 16384)), dim3(kBlock), 0, s, lab4, nd, vbase, E, cnt);
+        hipLaunchKernelGGL(k_regular_edges, dim3(grid_for(nd, kBlock, 16384)), dim3(kBlock), 0, s, lab4, nd, vbase, E,
+                           cnt);
         ROGTK_HIP_CHECK(hipGetLastError());
     }
     unsigned long long h[2];
@@ -464,16 +423,16 @@ int run_merge(const void* offs, const uint8_t* vals, const int64_t* rows, int64_
                   "irregular merge: a masked-key run longer than %d records (hash collisions)", kMaxRunWalk);
     const int64_t m = (int64_t)h[0];
     int64_t k = 0;
-    if (int rc = rogtk_cc_labels(n_reg + nd, (const uint32_t*)E, m, labels, &k, s)) return rc;
+    if (int rc = cc_labels(n_reg + nd, (const uint32_t*)E, m, labels, &k, s)) return rc;
     if (n_reg > 0 && relabel && relabel_n > 0) {
         uint32_t lastreg = 0;
         ROGTK_HIP_CHECK(hipMemcpyAsync(&lastreg, labels + n_reg - 1, 4, hipMemcpyDeviceToHost, s));
         ROGTK_HIP_CHECK(hipStreamSynchronize(s));
         if (lastreg != (uint32_t)(n_reg - 1))  // some regular clusters merged: remap their ids
-            hipLaunchKernelGGL(k_relabel, dim3(grid_for(relabel_n, 16384)), dim3(kBlock), 0, s, relabel, relabel_n,
-                               labels, (uint32_t)n_reg);
+            hipLaunchKernelGGL(k_relabel, dim3(grid_for(relabel_n, kBlock, 16384)), dim3(kBlock), 0, s, relabel,
+                               relabel_n, labels, (uint32_t)n_reg);
     }
-    hipLaunchKernelGGL(k_irr_write, dim3(grid_for(n, 1ll << 31)), dim3(kBlock), 0, s, rows, S.perm, S.rank, S.flag, n,
+    hipLaunchKernelGGL(k_irr_write, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, rows, S.perm, S.rank, S.flag, n,
                        labels, vbase, cluster_id);
     ROGTK_HIP_CHECK(hipGetLastError());
     ROGTK_HIP_CHECK(hipStreamSynchronize(s));
@@ -513,7 +472,8 @@ int irregular_merge(const void* offsets, int offset_width, const uint8_t* values
 int sorted_code_lookup(const uint64_t* G, int64_t ng, const uint32_t* labels, const uint64_t* q, int64_t nq,
                        uint32_t* lab, hipStream_t s) {
     if (nq <= 0) return ROGTK_OK;
-    hipLaunchKernelGGL(k_sorted_lookup, dim3(grid_for(nq, 16384)), dim3(kBlock), 0, s, G, ng, labels, q, nq, lab);
+    hipLaunchKernelGGL(k_sorted_lookup, dim3(grid_for(nq, kBlock, 16384)), dim3(kBlock), 0, s, G, ng, labels, q, nq,
+                       lab);
     ROGTK_HIP_CHECK(hipGetLastError());
     return ROGTK_OK;
 }

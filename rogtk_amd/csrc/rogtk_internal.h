@@ -384,6 +384,25 @@ int launch_cluster_lookup(const ClusterLayout& cl, const uint8_t* ws, const uint
 int masked_records_range(const uint64_t* D, int64_t nd, int p0, int np, uint64_t* mk, uint32_t* pos, uint64_t* code,
                          hipStream_t s);
 
+// dense labels of the connected components of nv vertices under m edges (uint2 pairs of
+// vertex indices, device), numbered in order of each component's smallest vertex
+// (dist_cluster.hip; rogtk_cc_labels is this behind the ABI's checks). Synchronises s.
+int cc_labels(int64_t nv, const uint32_t* edges, int64_t m, uint32_t* labels, int64_t* n_clusters, hipStream_t s);
+
+// The sort engines' front end (sorted_codes.hip): a device string column of n rows (1 <= n <
+// 2^31) -> the regular rows sorted by their 2-bit code (L 1..32; any other L: no row is
+// regular), the distinct codes D[m] ascending, every sorted row's index into D, the rows
+// per distinct code when want_counts, and the irregular row list; null rows' cluster_id =
+// 0xFFFFFFFF. Fields of SortedCodes: column_util.h. Synchronises s.
+// extra (nullable) sizes the caller's own per-code scratch once m is known: that many bytes
+// are added to out->codes_mem for the caller to take, which saves the engine an arena of its
+// own (each one is a real allocation and release; profiles/refactor_sort_engines.json).
+struct SortedCodes;
+using ExtraCodeBytes = std::function<int(int64_t m, size_t* bytes)>;
+int sorted_distinct_codes(const void* offsets, int ow, const uint8_t* values, const uint8_t* validity, int64_t voff,
+                          int64_t n, int L, bool want_counts, const ExtraCodeBytes* extra, uint32_t* cluster_id,
+                          SortedCodes* out, hipStream_t s);
+
 // H3 for 17 <= L <= 32 (sort-based, long_cluster.hip): regular + irregular rows of a
 // device column; ids into cid (device), *n_clusters on the host. Synchronises s.
 int long_cluster(const void* offsets, int ow, const uint8_t* values, const uint8_t* validity, int64_t voff,

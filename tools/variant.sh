@@ -14,8 +14,8 @@ for one in ${src//,/ }; do
         -Wno-unused-result -Wno-unused-value "$@" -c "$C/$one" -o "$T/${one%.hip}.o"
 done
 objs=""
-for o in capi umi_kernels cluster_kernels irregular kmer_kernels assembly fastq polars_plugin bam route long_cluster strings dist_cluster; do
-    if [ -f "$T/$o.o" ]; then objs="$objs $T/$o.o"; else objs="$objs $C/$o.o"; fi
+for o in $(make -s -C "$C" print-objs); do  # the Makefile's OBJS: one list
+    if [ -f "$T/$o" ]; then objs="$objs $T/$o"; else objs="$objs $C/$o"; fi
 done
 mkdir -p "$ROOT/tools/ab"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$ROOT/tools/ab/$name.so" $objs -lz -lpthread
