@@ -363,3 +363,42 @@ def test_bad_arguments_raise(rg):
         assert e.value.code == _lib.ROGTK_E_UNSUPPORTED
         with pytest.raises(ValueError):
             fn(_bin(KNOWN_ROWS), 4, 1, method="nonsense")
+
+
+# ------------------------------------------------------------ dense code sets, large counts
+# k_dir_edges bounds each binary search by |index(q) - v| <= |q - code|, which is tight only when
+# the code set is dense; and need = 2 count - 1 must not wrap at a u32 count (backend_cases.py).
+@pytest.mark.parametrize("L", [1, 2, 3, 4, 5])
+def test_full_grid_of_codes(rg, L):
+    """Every one of the 4^L codes is present: the search window of a neighbour d apart in value
+    is exactly d entries, its end is index m for the largest codes and index 0 for the smallest."""
+    from backend_cases import grid_counts
+    from directional_spec import roots_bfs
+
+    counts = dict(grid_counts(L))
+    assert len(counts) == 4 ** L
+    assert roots_fixed_point(counts) == roots_bfs(counts)
+    _check_codes(counts, L)
+
+
+@pytest.mark.parametrize("percent", [50, 90])
+def test_most_of_the_grid_at_length_6(rg, percent):
+    from backend_cases import grid_counts
+
+    counts = dict(grid_counts(6, percent))
+    assert len(counts) == 4096 * percent // 100
+    _check_codes(counts, 6)
+
+
+@pytest.mark.parametrize("name", ["edge_at_2_pow_31", "no_edge_above", "equal_maxima"])
+def test_counts_at_the_top_of_u32(rg, name):
+    """One pair of neighbours per case; the restatement computes 2 * count - 1 in Python integers."""
+    from backend_cases import LARGE_COUNT_PAIRS
+    from directional_spec import passes
+
+    (a, b), edge = LARGE_COUNT_PAIRS[name]
+    counts = {b"ACGA": a, b"ACGT": b}
+    assert passes(a, b) == edge and not passes(b, a)
+    want = roots_fixed_point(counts)
+    assert want[b"ACGT"] == (b"ACGA" if edge else b"ACGT") and want[b"ACGA"] == b"ACGA"
+    _check_codes(counts, 4)
