@@ -737,6 +737,60 @@ int rogtk_umi_correct_directional_host(const rogtk_str_col* col, int umi_len, in
                                        rogtk_u32_result* n_reads, rogtk_u32_result* n_distinct, int64_t* n_clusters,
                                        int* resolved_umi_len);
 
+/* ====== Clustering and correction within groups (grouped.hip; spec: DESIGN.md §4d) ======
+ * groups: one unsigned 32-bit key per row (a cell barcode's, gene's or position's dense id).
+ * No nulls, arbitrary values, equal keys need not be contiguous. Two rows may share a cluster
+ * only if their keys are equal; within one key the rule is that of the ungrouped call applied
+ * to the key's rows alone:
+ *   method 1 (directional), max_distance 0 or 1: the rule of §4c (0: no edges);
+ *   method 0 (cluster), max_distance 0: exact strings.
+ * method 0 with max_distance 1 is ROGTK_E_UNSUPPORTED before any device work (the transitive
+ * rule lets irregular strings bridge clusters; use method 1, "directional"), as is any other
+ * max_distance; any other method is ROGTK_E_INVALID.
+ * Ids: dense. The regular clusters first, ascending in (key, root code); then the distinct
+ * (key, irregular string) pairs, ascending in (key, bytes); 0xFFFFFFFF for a null row whatever
+ * its key. They depend on neither row order, chunking nor entry point, and with every key
+ * equal ids, tables and corrected values are those of the ungrouped call, bit for bit.
+ * cluster_group[c] = the key of cluster c. A cluster lies in one key and all its members
+ * have one byte length, so the §4b summary and gather take the ids as they are.
+ * Limits: n < 2^31 rows; the sort key (key << 2 umi_len | code) must fit 64 bits, that is
+ * 2 umi_len + bit_width(largest key of a regular row) <= 64: always for umi_len <= 16, for
+ * 17..32 it depends on the keys (ROGTK_E_UNSUPPORTED otherwise, found after the first kernel's
+ * read-back, before the sort). umi_len outside 1..32: every string is irregular.
+ * rogtk_directional_last_rounds reports these calls too (0 at max_distance 0). */
+
+/* Device column (layout as rogtk_umi_cluster_dev), groups[n] on the device. cluster_id[n],
+ * root_code (nullable, [n]: the 2-bit code of the row's root without the key, all ones for a
+ * null or irregular row) and cluster_group (nullable, capacity n; the first *n_clusters entries
+ * are written) on the device. Synchronises `stream`. */
+int rogtk_umi_cluster_grouped_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
+                                  const uint32_t* groups, int umi_len, int method, int max_distance,
+                                  uint32_t* cluster_id, int64_t* n_clusters, uint64_t* root_code,
+                                  uint32_t* cluster_group, void* stream);
+/* ids, then the §4b summary and gather (as rogtk_umi_correct_directional_dev) */
+int rogtk_umi_correct_grouped_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
+                                  const uint32_t* groups, int umi_len, int method, int max_distance,
+                                  uint32_t* cluster_id, int64_t* n_clusters, uint8_t* corrected_values,
+                                  uint32_t* cluster_group, void* stream);
+/* Host column: as rogtk_umi_cluster_directional_host / rogtk_umi_correct_directional_host with
+ * groups[n] on the host; cluster_group (nullable) is allocated by the library
+ * (rogtk_u32_result_free). */
+int rogtk_umi_cluster_grouped_host(const void* offsets, int offset_width, const uint8_t* values, int64_t values_len,
+                                   const uint8_t* validity, int64_t validity_offset, int64_t n,
+                                   const uint32_t* groups, int umi_len, int method, int max_distance,
+                                   uint32_t* cluster_id, int64_t* n_clusters, int* resolved_umi_len,
+                                   rogtk_u32_result* cluster_group);
+int rogtk_umi_correct_grouped_host(const rogtk_str_col* col, const uint32_t* groups, int umi_len, int method,
+                                   int max_distance, uint32_t* cluster_id, rogtk_str_result* corrected,
+                                   rogtk_str_result* representatives, rogtk_u32_result* n_reads,
+                                   rogtk_u32_result* n_distinct, rogtk_u32_result* cluster_group,
+                                   int64_t* n_clusters, int* resolved_umi_len);
+/* Measurements only: how the grouped edge search bounds its binary searches. 0: by value
+ * distance alone (the ungrouped bound), 1: clamped to the key's range of the sorted codes from
+ * a table of the key heads, 2: clamped to a range found by galloping out from the code (the
+ * default). The answers are the same. */
+int rogtk_grouped_set_window(int window);
+
 /* ============================== profiling ================================ */
 /* When enabled, every kernel launch is bracketed by HIP events on its stream. */
 /* ======== multi-GPU exchange of read groups ========
@@ -869,7 +923,8 @@ int rogtk_copy(void* dst, const void* src, int64_t bytes, void* stream);
  * (:770), sweep_assembly_params_expr (:880), optimize_assembly_expr
  * (fracture_opt.rs:283), and umi_correct_expr (no reference counterpart: the corrected UMI
  * of every row, kwargs umi_len / max_distance / method ("cluster", the default, or
- * "directional"), the whole series one batch). The structs are the Arrow C Data Interface and polars-ffi
+ * "directional"), the whole series one batch; an optional second input, an integer series
+ * of group keys 0..2^32-1 without nulls, makes it the grouped call of DESIGN.md §4d). The structs are the Arrow C Data Interface and polars-ffi
  * version_0's SeriesExport {ArrowSchema* field; ArrowArray** arrays; size_t len;
  * void (*release)(SeriesExport*); void* private_data;}; see INTEGRATION.md.
  * Diagnostics: the kwargs pickle as the plugin parses it, "key=value" lines. */

@@ -11,6 +11,7 @@ Drop-in surface (mirrors rogtk/__init__.py's `umi` / `hamming` namespaces):
     rg.umi_cluster(umis, max_distance=1)         # H3 (caller-side group_by('umi'))
     rg.umi_correct(umis, max_distance=1)         # representatives, sizes, corrected UMIs
     rg.umi_correct(umis, method="directional")   # count-aware clusters
+    rg.umi_correct(umis, method="directional", groups=cell_ids)  # within each key (§4d)
     rg.kmer_spectrum(reads, k=17, min_coverage=20, group_offsets=...)  # H4 (fracture.rs)
     rg.assemble_sequences(group_reads, k=13, min_coverage=1, method="compression")  # H5
     rg.assemble_column_groups(offsets, values, cluster_ids, k=10, min_coverage=5)  # H5, all groups

@@ -236,6 +236,14 @@ SIGNATURES = {
     "rogtk_umi_correct_directional_host": [ctypes.POINTER(StrCol), _i32, _i32, _vp, ctypes.POINTER(StrResult),
                                            ctypes.POINTER(StrResult), ctypes.POINTER(U32Result),
                                            ctypes.POINTER(U32Result), _P_I64, _P_I32],
+    "rogtk_umi_cluster_grouped_dev": [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _vp, _P_I64, _vp, _vp, _vp],
+    "rogtk_umi_correct_grouped_dev": [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _vp, _P_I64, _vp, _vp, _vp],
+    "rogtk_umi_cluster_grouped_host": [_vp, _i32, _vp, _i64, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _vp, _P_I64,
+                                       _P_I32, ctypes.POINTER(U32Result)],
+    "rogtk_umi_correct_grouped_host": [ctypes.POINTER(StrCol), _vp, _i32, _i32, _i32, _vp, ctypes.POINTER(StrResult),
+                                       ctypes.POINTER(StrResult), ctypes.POINTER(U32Result),
+                                       ctypes.POINTER(U32Result), ctypes.POINTER(U32Result), _P_I64, _P_I32],
+    "rogtk_grouped_set_window": [_i32],
     "rogtk_profile_enable": [_i32],
     "rogtk_profile_select": [ctypes.c_char_p],
     "rogtk_profile_reset": [],

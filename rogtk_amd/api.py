@@ -39,7 +39,7 @@ import numpy as np
 import pyarrow as pa
 
 from . import _lib
-from .columns import ColumnLike, chunks, concat, validity_buffer
+from .columns import ColumnLike, _to_arrow, chunks, concat, validity_buffer
 
 FIELDS = (
     ("shannon_entropy", pa.float64()),
@@ -176,14 +176,54 @@ def umi_method_entry(method: str, max_distance: int, cluster_entry: str, directi
     return directional_entry
 
 
-def umi_cluster(column: ColumnLike, umi_len: int = 0, max_distance: int = 1, method: str = "cluster"):
+def group_keys(groups, n: int) -> np.ndarray:
+    """The ``groups`` argument of the grouped calls as n contiguous uint32 keys:
+    a numpy or Arrow integer array (or chunked array) of the column's length, values in
+    0..2^32-1, no nulls. Anything else is a ValueError, before the library is called."""
+    if isinstance(groups, pa.ChunkedArray):
+        groups = groups.combine_chunks() if groups.num_chunks else pa.array([], type=groups.type)
+    if isinstance(groups, pa.Array):
+        if not pa.types.is_integer(groups.type):
+            raise ValueError(f"groups must be an integer array, got {groups.type}")
+        if groups.null_count:
+            raise ValueError(f"groups has {groups.null_count} null keys; every row needs a key")
+        groups = groups.to_numpy(zero_copy_only=False)
+    g = np.asarray(groups)
+    if g.dtype.kind not in "iu":
+        raise ValueError(f"groups must be an integer array, got dtype {g.dtype}")
+    if g.shape != (n,):
+        raise ValueError(f"groups has shape {g.shape}, the column has {n} rows")
+    if g.size and (int(g.min()) < 0 or int(g.max()) > 0xFFFFFFFF):
+        raise ValueError("groups must hold values in 0..2^32-1")
+    return np.ascontiguousarray(g, dtype=np.uint32)
+
+
+def grouped_method(method: str, max_distance: int) -> int:
+    """The C ``method`` of a grouped call (0 cluster, 1 directional); what the library would
+    refuse is refused here, before any buffer is allocated."""
+    if method not in UMI_METHODS:
+        raise ValueError(f"method must be one of {UMI_METHODS}, got {method!r}")
+    if int(max_distance) not in (0, 1):
+        raise _lib.RogtkError(_lib.ROGTK_E_UNSUPPORTED, f"max_distance {max_distance}: only 0 and 1 are supported")
+    if method == "cluster" and int(max_distance) == 1:
+        raise _lib.RogtkError(_lib.ROGTK_E_UNSUPPORTED,
+                              'method="cluster" with max_distance 1 is not supported within groups; '
+                              'use method="directional"')
+    return UMI_METHODS.index(method)
+
+
+def umi_cluster(column: ColumnLike, umi_len: int = 0, max_distance: int = 1, method: str = "cluster", groups=None):
     """H3 cluster id per row: dense ids, exact (0) or Hamming<=1 components (1).
     method="directional": the count-aware rule at one edit; an abundant UMI
     absorbs a neighbour only when count(abundant) >= 2 * count(neighbour) - 1.
+    groups (one unsigned 32-bit key per row): rows cluster only with rows of
+    the same key; method="directional" at max_distance 0 or 1, method="cluster" at 0.
 
     Returns (pa.UInt32Array with nulls for null rows, n_clusters, resolved umi_len).
     A multi-chunk column is clustered as one batch (ids are global to the column).
     """
+    if groups is not None:
+        return _umi_cluster_grouped(column, umi_len, max_distance, method, groups)
     entry = umi_method_entry(method, max_distance, "rogtk_umi_cluster_host", "rogtk_umi_cluster_directional_host")
     arr = column
     if isinstance(arr, pa.ChunkedArray):
@@ -198,6 +238,24 @@ def umi_cluster(column: ColumnLike, umi_len: int = 0, max_distance: int = 1, met
     o, v, val = ch.ptrs()
     _lib.call(entry, o, ch.offset_width, v, ch.values.size, val, ch.validity_offset,
               n, int(umi_len), int(max_distance), _ptr(cid), ctypes.byref(nclu), ctypes.byref(rl))
+    out = pa.Array.from_buffers(pa.uint32(), n, [validity_buffer(ch), pa.py_buffer(cid)])
+    return out, int(nclu.value), int(rl.value)
+
+
+def _umi_cluster_grouped(column, umi_len, max_distance, method, groups):
+    m = grouped_method(method, max_distance)
+    arr = _to_arrow(column)
+    if isinstance(arr, pa.ChunkedArray):
+        arr = arr.combine_chunks() if arr.num_chunks else pa.array([], type=arr.type)
+    ch = next(iter(chunks(arr)))
+    n = ch.n
+    keys = group_keys(groups, n)
+    cid = _out(n, np.uint32)
+    nclu, rl = ctypes.c_int64(0), ctypes.c_int(0)
+    o, v, val = ch.ptrs()
+    _lib.call("rogtk_umi_cluster_grouped_host", o, ch.offset_width, v, ch.values.size, val, ch.validity_offset, n,
+              _ptr(keys) if n else None, int(umi_len), m, int(max_distance), _ptr(cid), ctypes.byref(nclu),
+              ctypes.byref(rl), None)
     out = pa.Array.from_buffers(pa.uint32(), n, [validity_buffer(ch), pa.py_buffer(cid)])
     return out, int(nclu.value), int(rl.value)
 
@@ -277,16 +335,17 @@ class UmiNamespace:
     def dust_score(self):
         return self._one("dust_score")
 
-    def cluster(self, umi_len: int = 0, max_distance: int = 1, method: str = "cluster"):
-        """Extension (no reference counterpart): H3 cluster ids ("directional": DESIGN.md §4c)."""
-        return umi_cluster(self._c, umi_len, max_distance, method)[0]
+    def cluster(self, umi_len: int = 0, max_distance: int = 1, method: str = "cluster", groups=None):
+        """Extension (no reference counterpart): H3 cluster ids ("directional": DESIGN.md §4c;
+        groups: within each key, §4d)."""
+        return umi_cluster(self._c, umi_len, max_distance, method, groups)[0]
 
-    def correct(self, umi_len: int = 0, max_distance: int = 1, method: str = "cluster"):
+    def correct(self, umi_len: int = 0, max_distance: int = 1, method: str = "cluster", groups=None):
         """Extension (no reference counterpart): every row's UMI replaced by the
-        representative of its cluster (method="directional": §4c)."""
+        representative of its cluster (method="directional": §4c; groups: §4d)."""
         from .correct import umi_correct
 
-        return umi_correct(self._c, umi_len, max_distance, method).corrected
+        return umi_correct(self._c, umi_len, max_distance, method, groups).corrected
 
 
 class HammingExpr:

@@ -15,6 +15,8 @@ host (rogtk/__init__.py:206-214).
     rg.umi_cluster_summary(umis, my_ids)          # the same table for the caller's ids
     rg.col(umis).umi.correct(max_distance=1)      # the corrected column alone
     rg.umi_correct(umis, method="directional")    # count-aware clusters
+    rg.umi_correct(umis, 12, method="directional", groups=cell_ids)   # within each key (§4d);
+                                                  # clusters then has a fourth field, group
 """
 from __future__ import annotations
 
@@ -85,11 +87,50 @@ def _clusters(reps, n_reads, n_distinct, typ) -> pa.StructArray:
                                       names=list(CLUSTER_FIELDS))
 
 
+def _umi_correct_grouped(column, umi_len, max_distance, method, groups) -> UmiCorrection:
+    from .api import group_keys, grouped_method
+
+    m = grouped_method(method, max_distance)
+    ch = _one_chunk(column)
+    n = ch.n
+    keys = group_keys(groups, n)
+    cid = np.zeros(max(n, 1), dtype=np.uint32)
+    corrected, reps = _lib.StrResult(), _lib.StrResult()
+    n_reads, n_distinct, cgroup = _lib.U32Result(), _lib.U32Result(), _lib.U32Result()
+    nclu, rl = ctypes.c_int64(0), ctypes.c_int(0)
+    desc = _desc(ch)
+    lib = _lib.hip()
+    _lib.check(lib.rogtk_umi_correct_grouped_host(
+        ctypes.byref(desc), ctypes.c_void_p(keys.ctypes.data) if n else None, int(umi_len), m, int(max_distance),
+        ctypes.c_void_p(cid.ctypes.data), ctypes.byref(corrected), ctypes.byref(reps), ctypes.byref(n_reads),
+        ctypes.byref(n_distinct), ctypes.byref(cgroup), ctypes.byref(nclu), ctypes.byref(rl)))
+    try:
+        typ = _text_type(ch)
+        out = _take_str(corrected, typ)
+        k = int(nclu.value)
+        group = (np.ctypeslib.as_array(ctypes.cast(cgroup.data, ctypes.POINTER(ctypes.c_uint32)), (k,)).copy()
+                 if k else np.zeros(0, np.uint32))
+        clusters = pa.StructArray.from_arrays(
+            [_take_str(reps, typ), _take_u32(n_reads), _take_u32(n_distinct), pa.array(group, type=pa.uint32())],
+            names=list(CLUSTER_FIELDS) + ["group"])
+    finally:
+        lib.rogtk_str_result_free(ctypes.byref(corrected))
+        lib.rogtk_str_result_free(ctypes.byref(reps))
+        for r in (n_reads, n_distinct, cgroup):
+            lib.rogtk_u32_result_free(ctypes.byref(r))
+    ids = pa.Array.from_buffers(pa.uint32(), n, [validity_buffer(ch), pa.py_buffer(cid[:n])])
+    return UmiCorrection(out, ids, int(nclu.value), clusters, int(rl.value))
+
+
 def umi_correct(column: ColumnLike, umi_len: int = 0, max_distance: int = 1,
-                method: str = "cluster") -> UmiCorrection:
+                method: str = "cluster", groups=None) -> UmiCorrection:
     """Clusters of the column (as ``umi_cluster``: method="cluster" the H3 components,
     "directional" the count-aware rule of DESIGN.md §4c), their summary and the corrected
-    UMI of every row. A multi-chunk column is one batch."""
+    UMI of every row. A multi-chunk column is one batch. groups (one unsigned 32-bit key per
+    row): clusters form within each key, and ``clusters`` gains a fourth field
+    ``group``, the key of every cluster."""
+    if groups is not None:
+        return _umi_correct_grouped(column, umi_len, max_distance, method, groups)
     from .api import umi_method_entry
 
     entry = umi_method_entry(method, max_distance, "rogtk_umi_correct_host", "rogtk_umi_correct_directional_host")

@@ -394,6 +394,7 @@ struct HostCtx {
     int device = -1;
     hipStream_t stream = nullptr;
     DevBuf offsets, values, validity, codes, regbits, irr, nirr, target, out[8], ws, bitmap;
+    DevBuf grp[2];  // the grouped entries: the rows' keys, the clusters' keys
     int64_t ws_L = -1, ws_maxd = -1;
     void* pin[2] = {nullptr, nullptr};  // staging for pageable host memory
     hipEvent_t ev[2] = {nullptr, nullptr};
@@ -1319,12 +1320,44 @@ int rogtk_cluster_summary_host(const rogtk_str_col* col, int umi_len, const uint
 namespace {
 thread_local int64_t t_directional_rounds = 0;  // rogtk_directional_last_rounds
 
+// the argument rules of the grouped entries (include/rogtk_hip.h), before any device work
+static int check_grouped(const char* name, int method, int max_distance) {
+    ROGTK_REQUIRE(method == 0 || method == 1, ROGTK_E_INVALID, "%s: method %d is neither 0 (cluster) nor 1 (directional)",
+                  name, method);
+    ROGTK_REQUIRE(max_distance == 0 || max_distance == 1, ROGTK_E_UNSUPPORTED,
+                  "max_distance %d: only 0 and 1 are supported", max_distance);
+    ROGTK_REQUIRE(method == 1 || max_distance == 0, ROGTK_E_UNSUPPORTED,
+                  "%s: method=\"cluster\" with max_distance 1 is not supported within groups (irregular strings "
+                  "bridge clusters under the transitive rule); use method=\"directional\"",
+                  name);
+    return ROGTK_OK;
+}
+
+// the keys of a host column on the device (c->grp[0]) and room for the clusters' keys (c->grp[1])
+static int upload_groups(HostCtx* c, const uint32_t* groups, int64_t n) {
+    const size_t b = (size_t)std::max<int64_t>(n, 1) * 4;
+    if (int rc = c->grp[0].ensure(b)) return rc;
+    if (int rc = c->grp[1].ensure(b)) return rc;
+    return c->h2d(c->grp[0].p, groups, (size_t)n * 4);
+}
+
+static int groups_to_host(HostCtx* c, int64_t nclu, rogtk_u32_result* cluster_group) {
+    if (!cluster_group) return ROGTK_OK;
+    cluster_group->n = nclu;
+    cluster_group->data = (uint32_t*)calloc((size_t)std::max<int64_t>(nclu, 1), 4);
+    ROGTK_REQUIRE(cluster_group->data, ROGTK_E_INVALID, "out of host memory");
+    return c->d2h(cluster_group->data, c->grp[1].p, (size_t)nclu * 4);
+}
+
 // rogtk_umi_correct_host (directional = false) and rogtk_umi_correct_directional_host at
-// max_distance 1 (directional = true): they differ in the ids alone.
+// max_distance 1 (directional = true): they differ in the ids alone. groups (nullable): the
+// grouped ids (rogtk_umi_correct_grouped_host) and the clusters' keys into cluster_group.
 static int correct_host(const rogtk_str_col* col, int umi_len, int max_distance, bool directional, uint32_t* cluster_id,
                         rogtk_str_result* corrected, rogtk_str_result* representatives, rogtk_u32_result* n_reads,
-                        rogtk_u32_result* n_distinct, int64_t* n_clusters, int* resolved_umi_len) {
+                        rogtk_u32_result* n_distinct, int64_t* n_clusters, int* resolved_umi_len,
+                        const uint32_t* groups = nullptr, rogtk_u32_result* cluster_group = nullptr) {
     if (int rc = check_correct_outputs(col, representatives, n_reads, n_distinct)) return rc;
+    u32_result_reset(cluster_group);
     ROGTK_REQUIRE(corrected, ROGTK_E_INVALID, "NULL output (corrected is required)");
     *corrected = rogtk_str_result{};
     HostCol h{col->offsets, col->offset_width, col->values, col->values_len, col->validity, col->validity_offset,
@@ -1350,7 +1383,14 @@ static int correct_host(const rogtk_str_col* col, int umi_len, int max_distance,
             if (int rc = upload_and_stage(c, h, L, &L, &n_irr)) return rc;
             if (int rc = device_max_len(c, h.ow, n, &max_len)) return rc;
             dvalid = h.validity ? c->validity.as<uint8_t>() : nullptr;
-            if (directional) {
+            if (groups) {
+                if (int rc = upload_groups(c, groups, n)) return rc;
+                if (int rc = grouped_cluster(c->offsets.p, h.ow, c->values.as<uint8_t>(), dvalid, h.voff, n, L,
+                                             c->grp[0].as<uint32_t>(), max_distance, did, nullptr,
+                                             c->grp[1].as<uint32_t>(), &nclu, &t_directional_rounds, nullptr,
+                                             c->stream))
+                    return rc;
+            } else if (directional) {
                 if (int rc = directional_cluster(c->offsets.p, h.ow, c->values.as<uint8_t>(), dvalid, h.voff, n, L,
                                                  did, nullptr, &nclu, &t_directional_rounds, nullptr, c->stream))
                     return rc;
@@ -1361,6 +1401,8 @@ static int correct_host(const rogtk_str_col* col, int umi_len, int max_distance,
             if (int rc = c->d2h(cluster_id, did, (size_t)n * 4)) return rc;
         }
         if (n_clusters) *n_clusters = nclu;
+        if (groups)
+            if (int rc = groups_to_host(c, nclu, cluster_group)) return rc;
         if (int rc = summary_to_host(c, c->offsets.p, h.ow, c->values.as<uint8_t>(), dvalid, h.voff, n, L, did, nclu,
                                      max_len, representatives, n_reads, n_distinct))
             return rc;
@@ -1393,6 +1435,7 @@ static int correct_host(const rogtk_str_col* col, int umi_len, int max_distance,
         rogtk_str_result_free(representatives);
         rogtk_u32_result_free(n_reads);
         rogtk_u32_result_free(n_distinct);
+        rogtk_u32_result_free(cluster_group);
     }
     return rc;
 }
@@ -1595,6 +1638,101 @@ int rogtk_umi_correct_directional_host(const rogtk_str_col* col, int umi_len, in
                                        int* resolved_umi_len) {
     return correct_host(col, umi_len, max_distance, max_distance == 1, cluster_id, corrected, representatives, n_reads,
                         n_distinct, n_clusters, resolved_umi_len);
+}
+
+// ------------------------------------ clustering within groups (grouped.hip)
+int rogtk_grouped_set_window(int window) { return grouped_set_window(window); }
+
+int rogtk_umi_cluster_grouped_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
+                                  const uint32_t* groups, int umi_len, int method, int max_distance,
+                                  uint32_t* cluster_id, int64_t* n_clusters, uint64_t* root_code,
+                                  uint32_t* cluster_group, void* stream) {
+    if (int rc = check_rows_and_clusters("umi_cluster_grouped_dev", n, 0)) return rc;
+    if (int rc = check_grouped("umi_cluster_grouped_dev", method, max_distance)) return rc;
+    ROGTK_REQUIRE(n == 0 || (offsets && values && cluster_id && groups), ROGTK_E_INVALID,
+                  "umi_cluster_grouped_dev: NULL argument");
+    ROGTK_REQUIRE(umi_len >= 1, ROGTK_E_INVALID, "umi_cluster_grouped_dev: umi_len must be >= 1");
+    int64_t nclu = 0;
+    t_directional_rounds = 0;
+    if (n_clusters) *n_clusters = 0;
+    if (n == 0) return ROGTK_OK;
+    if (int rc = grouped_cluster(offsets, 8, values, validity, 0, n, umi_len, groups, max_distance, cluster_id,
+                                 root_code, cluster_group, &nclu, &t_directional_rounds, nullptr, as_stream(stream)))
+        return rc;
+    if (n_clusters) *n_clusters = nclu;
+    return ROGTK_OK;
+}
+
+int rogtk_umi_correct_grouped_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
+                                  const uint32_t* groups, int umi_len, int method, int max_distance,
+                                  uint32_t* cluster_id, int64_t* n_clusters, uint8_t* corrected_values,
+                                  uint32_t* cluster_group, void* stream) {
+    if (int rc = check_rows_and_clusters("umi_correct_grouped_dev", n, 0)) return rc;
+    if (int rc = check_grouped("umi_correct_grouped_dev", method, max_distance)) return rc;
+    ROGTK_REQUIRE(n == 0 || (offsets && values && cluster_id && corrected_values && groups), ROGTK_E_INVALID,
+                  "umi_correct_grouped_dev: NULL argument");
+    ROGTK_REQUIRE(umi_len >= 1, ROGTK_E_INVALID, "umi_correct_grouped_dev: umi_len must be >= 1");
+    if (n_clusters) *n_clusters = 0;
+    t_directional_rounds = 0;
+    if (n == 0) return ROGTK_OK;
+    hipStream_t s = as_stream(stream);
+    HostCtx* c;
+    if (int rc = host_ctx(&c)) return rc;
+    int64_t nclu = 0, max_len = 0;
+    if (int rc = grouped_cluster(offsets, 8, values, validity, 0, n, umi_len, groups, max_distance, cluster_id, nullptr,
+                                 cluster_group, &nclu, &t_directional_rounds, &max_len, s))
+        return rc;
+    if (n_clusters) *n_clusters = nclu;
+    return correct_tail_dev(c, offsets, values, validity, n, umi_len, cluster_id, nclu, max_len, corrected_values, s);
+}
+
+int rogtk_umi_cluster_grouped_host(const void* offsets, int offset_width, const uint8_t* values, int64_t values_len,
+                                   const uint8_t* validity, int64_t validity_offset, int64_t n,
+                                   const uint32_t* groups, int umi_len, int method, int max_distance,
+                                   uint32_t* cluster_id, int64_t* n_clusters, int* resolved_umi_len,
+                                   rogtk_u32_result* cluster_group) {
+    u32_result_reset(cluster_group);
+    if (int rc = check_grouped("umi_cluster_grouped", method, max_distance)) return rc;
+    HostCol h{offsets, offset_width, values, values_len, validity, validity_offset, n};
+    if (int rc = check_host_col(h)) return rc;
+    ROGTK_REQUIRE(n < (1ll << 31), ROGTK_E_UNSUPPORTED, "umi_cluster_grouped: at most 2^31 - 1 rows");
+    ROGTK_REQUIRE((cluster_id && groups) || n == 0, ROGTK_E_INVALID, "cluster_id or groups is NULL");
+    int L = umi_len > 0 ? umi_len : h.first_len();
+    if (resolved_umi_len) *resolved_umi_len = L;
+    if (n_clusters) *n_clusters = 0;
+    t_directional_rounds = 0;
+    if (n == 0) return ROGTK_OK;
+    HostCtx* c;
+    if (int rc = host_ctx(&c)) return rc;
+    if (int rc = upload_and_stage(c, h, L, &L, nullptr)) return rc;
+    if (int rc = c->out[0].ensure((size_t)std::max<int64_t>(n, 4) * 4)) return rc;
+    if (int rc = upload_groups(c, groups, n)) return rc;
+    uint32_t* did = c->out[0].as<uint32_t>();
+    int64_t nclu = 0;
+    if (int rc = grouped_cluster(c->offsets.p, offset_width, c->values.as<uint8_t>(),
+                                 h.validity ? c->validity.as<uint8_t>() : nullptr, h.voff, n, L,
+                                 c->grp[0].as<uint32_t>(), max_distance, did, nullptr, c->grp[1].as<uint32_t>(), &nclu,
+                                 &t_directional_rounds, nullptr, c->stream))
+        return rc;
+    if (n_clusters) *n_clusters = nclu;
+    if (int rc = c->d2h(cluster_id, did, (size_t)n * 4)) return rc;
+    const int rc = groups_to_host(c, nclu, cluster_group);
+    if (rc) rogtk_u32_result_free(cluster_group);
+    return rc;
+}
+
+int rogtk_umi_correct_grouped_host(const rogtk_str_col* col, const uint32_t* groups, int umi_len, int method,
+                                   int max_distance, uint32_t* cluster_id, rogtk_str_result* corrected,
+                                   rogtk_str_result* representatives, rogtk_u32_result* n_reads,
+                                   rogtk_u32_result* n_distinct, rogtk_u32_result* cluster_group,
+                                   int64_t* n_clusters, int* resolved_umi_len) {
+    u32_result_reset(cluster_group);
+    if (int rc = check_grouped("umi_correct_grouped", method, max_distance)) return rc;
+    ROGTK_REQUIRE(groups || !col || col->n == 0, ROGTK_E_INVALID, "umi_correct_grouped: groups is NULL");
+    static const uint32_t no_rows = 0;  // an empty column still takes the grouped path
+    t_directional_rounds = 0;
+    return correct_host(col, umi_len, max_distance, true, cluster_id, corrected, representatives, n_reads, n_distinct,
+                        n_clusters, resolved_umi_len, groups ? groups : &no_rows, cluster_group);
 }
 
 // --------------------------------------------------------------- stream events

@@ -74,6 +74,8 @@ struct SortedCodes {
     int64_t n_irr = 0;        // the other valid rows
     int64_t max_irr_len = 0;  // byte length of the longest irregular row
     int64_t m = 0;            // distinct codes of the regular rows
+    int key_bits = 0;         // bits the sort ran over (grouped: 2 L + bit_width(max_group))
+    uint32_t max_group = 0, max_irr_group = 0;  // grouped: largest key of the regular / irregular rows
     const int64_t* irr = nullptr;   // [n_irr] the irregular rows, in any order
     const uint32_t* row = nullptr;  // [n_reg] the regular rows, ascending in their code
     const uint32_t* idx = nullptr;  // [n_reg] index into D of row[k]'s code

@@ -42,15 +42,60 @@ __device__ __forceinline__ unsigned long long dir_key(uint32_t count, uint32_t v
 }
 __device__ __forceinline__ uint32_t dir_index(unsigned long long key) { return 0xFFFFFFFFu - (uint32_t)key; }
 
+// WINDOW: D holds composites key << shift | code. A substitution changes the
+// low digits alone, so a neighbour lies among the entries of the lane's own key, [gb, ge):
+// kWindowTable reads that range from the table of key heads, kWindowGallop finds it by
+// doubling steps out from v and a binary search of the last step. The value bound below is
+// then clamped to it: for the high digits it is the whole array otherwise. kWindowValue is
+// the ungrouped kernel, unchanged.
+template <int WINDOW>
 __global__ void __launch_bounds__(kBlock)
 k_dir_edges(const uint64_t* __restrict__ D, const uint32_t* __restrict__ C, int64_t m, int L,
-            uint32_t* __restrict__ deg, uint32_t* __restrict__ adj, unsigned long long* __restrict__ best) {
+            uint32_t* __restrict__ deg, uint32_t* __restrict__ adj, unsigned long long* __restrict__ best,
+            int shift, const uint32_t* __restrict__ gidx, const uint32_t* __restrict__ gstart) {
     const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (v >= m) return;
     const uint64_t code = D[v];
     const uint32_t cv = C[v];
     const uint64_t need = 2ull * (uint64_t)cv - 1ull;  // count(u) >= 2 count(v) - 1, in 64 bits
     uint32_t nd = 0;
+    [[maybe_unused]] int64_t gb = 0, ge = m;
+    if constexpr (WINDOW == kWindowTable) {
+        const uint32_t g = gidx[v];
+        gb = gstart[g];
+        ge = gstart[g + 1];
+    } else if constexpr (WINDOW == kWindowGallop) {
+        if (shift < 64) {
+            const uint64_t first = (code >> shift) << shift;      // the key's smallest composite
+            const uint64_t last = first | ((1ull << shift) - 1);  // and its largest
+            int64_t step = 1, hi = v;                             // D[hi] >= first
+            while (hi - step >= 0 && D[hi - step] >= first) {
+                hi -= step;
+                step <<= 1;
+            }
+            int64_t lo = hi - step >= 0 ? hi - step + 1 : 0;  // D[lo - 1] < first (or lo == 0)
+            while (lo < hi) {                                 // first index with D[index] >= first
+                const int64_t mid = (lo + hi) >> 1;
+                if (D[mid] < first) lo = mid + 1;
+                else hi = mid;
+            }
+            gb = lo;
+            step = 1;
+            lo = v;  // D[lo] <= last
+            while (lo + step < m && D[lo + step] <= last) {
+                lo += step;
+                step <<= 1;
+            }
+            hi = lo + step < m ? lo + step : m;  // D[hi] > last (or hi == m)
+            ++lo;
+            while (lo < hi) {  // first index with D[index] > last
+                const int64_t mid = (lo + hi) >> 1;
+                if (D[mid] <= last) lo = mid + 1;
+                else hi = mid;
+            }
+            ge = lo;
+        }
+    }
     for (int p = 0; p < L; ++p) {
         for (uint64_t x = 1; x <= 3; ++x) {
             const uint64_t q = code ^ (x << (2 * p));
@@ -65,12 +110,16 @@ k_dir_edges(const uint64_t* __restrict__ D, const uint32_t* __restrict__ C, int6
                 lo = v + 1;
                 hi = d < (uint64_t)(m - v) ? v + (int64_t)d + 1 : m;
             }
+            if constexpr (WINDOW != kWindowValue) {
+                lo = max(lo, gb);
+                hi = min(hi, ge);
+            }
             while (lo < hi) {  // first index in [lo, hi) with D[index] >= q
                 const int64_t mid = (lo + hi) >> 1;
                 if (D[mid] < q) lo = mid + 1;
                 else hi = mid;
             }
-            if (lo < m && D[lo] == q && (uint64_t)C[lo] >= need) {
+            if (lo < (WINDOW != kWindowValue ? ge : m) && D[lo] == q && (uint64_t)C[lo] >= need) {
                 adj[(int64_t)nd * m + v] = (uint32_t)lo;
                 ++nd;
             }
@@ -179,7 +228,8 @@ int directional_codes_temp(int64_t m, int L, int64_t* bytes) {
 }
 
 int directional_codes(const uint64_t* D, const uint32_t* C, int64_t m, int L, uint32_t* root, uint32_t* labels,
-                      int64_t* n_clusters, int64_t* rounds, void* temp, int64_t temp_bytes, hipStream_t s) {
+                      int64_t* n_clusters, int64_t* rounds, void* temp, int64_t temp_bytes, hipStream_t s,
+                      const DirGroups* grp) {
     *n_clusters = 0;
     *rounds = 0;
     if (m <= 0) return ROGTK_OK;
@@ -195,7 +245,15 @@ int directional_codes(const uint64_t* D, const uint32_t* C, int64_t m, int L, ui
     uint32_t* rank = (uint32_t*)(t + p.off_rank);
     uint32_t* adj = (uint32_t*)(t + p.off_adj);
     const dim3 g(grid_for(m, kBlock)), b(kBlock);
-    hipLaunchKernelGGL(k_dir_edges, g, b, 0, s, D, C, m, L, deg, adj, best);
+    const uint32_t* no_table = nullptr;
+    if (grp && grp->window == kWindowTable)
+        hipLaunchKernelGGL(k_dir_edges<kWindowTable>, g, b, 0, s, D, C, m, L, deg, adj, best, grp->shift, grp->gidx,
+                           grp->gstart);
+    else if (grp && grp->window == kWindowGallop)
+        hipLaunchKernelGGL(k_dir_edges<kWindowGallop>, g, b, 0, s, D, C, m, L, deg, adj, best, grp->shift, no_table,
+                           no_table);
+    else
+        hipLaunchKernelGGL(k_dir_edges<kWindowValue>, g, b, 0, s, D, C, m, L, deg, adj, best, 0, no_table, no_table);
     ROGTK_HIP_CHECK(hipGetLastError());
     auto launch = [&](int64_t, int k) -> int {
         ROGTK_HIP_CHECK(hipMemsetAsync(ctrl, 0, 16, s));

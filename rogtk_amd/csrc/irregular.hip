@@ -350,6 +350,87 @@ int run_exact(const void* offs, const uint8_t* vals, const int64_t* rows, int64_
     return ROGTK_OK;
 }
 
+// ------------------------------------------------------------ within groups
+// sorted position k -> (key of its row << rank_bits | rank of its string, its row)
+__global__ void k_irr_group_keys(const int64_t* __restrict__ rows, const uint32_t* __restrict__ perm,
+                                 const uint32_t* __restrict__ rank, const uint32_t* __restrict__ flag, int64_t n,
+                                 const uint32_t* __restrict__ groups, int rank_bits, uint64_t* __restrict__ key,
+                                 uint32_t* __restrict__ val) {
+    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (k >= n) return;
+    const int64_t r = rows[perm[k]];
+    key[k] = ((uint64_t)groups[r] << rank_bits) | (uint64_t)(rank[k] + flag[k] - 1u);
+    val[k] = (uint32_t)r;
+}
+
+__global__ void k_irr_group_heads(const uint64_t* __restrict__ skey, int64_t n, uint32_t* __restrict__ flag) {
+    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (k >= n) return;
+    flag[k] = k == 0 || skey[k] != skey[k - 1];
+}
+
+// every copy of a (key, string) pair gets the id of its head; the head writes the pair's key
+__global__ void k_irr_group_assign(const uint64_t* __restrict__ skey, const uint32_t* __restrict__ sval,
+                                   const uint32_t* __restrict__ rank, const uint32_t* __restrict__ flag, int64_t n,
+                                   int rank_bits, uint32_t base, uint32_t* __restrict__ out,
+                                   uint32_t* __restrict__ cluster_group, uint32_t* __restrict__ total) {
+    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (k >= n) return;
+    const uint32_t id = base + rank[k] + flag[k] - 1u;
+    out[sval[k]] = id;
+    if (flag[k] && cluster_group) cluster_group[id] = (uint32_t)(skey[k] >> rank_bits);
+    if (k == n - 1) *total = rank[k] + flag[k];
+}
+
+int bit_width_u64(uint64_t v) {
+    int b = 0;
+    while (b < 64 && (v >> b)) ++b;
+    return b;
+}
+
+// The strings are ranked by bytes across the column (sort_strings); a second sort of
+// key << rank_bits | rank over the bits in use puts the pairs in (key, bytes) order.
+template <int OW>
+int run_exact_grouped(const void* offs, const uint8_t* vals, const int64_t* rows, int64_t n, int64_t max_len,
+                      const uint32_t* groups, uint32_t max_group, uint32_t id_base, uint32_t* cluster_id,
+                      uint32_t* cluster_group, int64_t* n_out, hipStream_t s) {
+    StringSort S;
+    if (int rc = sort_strings<OW>(offs, vals, rows, n, max_len, S, s)) return rc;
+    const int rank_bits = std::max(1, bit_width_u64((uint64_t)(S.distinct - 1)));
+    const int bits = rank_bits + bit_width_u64(max_group);
+    size_t sort_b = 0, scan_b = 0;
+    ROGTK_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_b, (uint64_t*)nullptr, (uint64_t*)nullptr,
+                                                       (uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, bits, s));
+    ROGTK_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)n,
+                                                     s));
+    const size_t tmp_b = std::max(sort_b, scan_b);
+    Arena M;
+    if (int rc = M.get(al(256) + 2 * al((size_t)n * 8) + 4 * al((size_t)n * 4) + al(tmp_b), s)) return rc;
+    uint32_t* total = M.take<uint32_t>(64);
+    uint64_t* key = M.take<uint64_t>(n);
+    uint64_t* skey = M.take<uint64_t>(n);
+    uint32_t* val = M.take<uint32_t>(n);
+    uint32_t* sval = M.take<uint32_t>(n);
+    uint32_t* flag = M.take<uint32_t>(n);
+    uint32_t* rank = M.take<uint32_t>(n);
+    void* tmp = M.take<uint8_t>((int64_t)tmp_b);
+    const dim3 g(grid_for(n, kBlock)), b(kBlock);
+    hipLaunchKernelGGL(k_irr_group_keys, g, b, 0, s, rows, S.perm, S.rank, S.flag, n, groups, rank_bits, key, val);
+    size_t tb = tmp_b;
+    ROGTK_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key, skey, val, sval, (int)n, 0, bits, s));
+    hipLaunchKernelGGL(k_irr_group_heads, g, b, 0, s, skey, n, flag);
+    tb = tmp_b;
+    ROGTK_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, flag, rank, (int)n, s));
+    hipLaunchKernelGGL(k_irr_group_assign, g, b, 0, s, skey, sval, rank, flag, n, rank_bits, id_base, cluster_id,
+                       cluster_group, total);
+    ROGTK_HIP_CHECK(hipGetLastError());
+    uint32_t h = 0;
+    ROGTK_HIP_CHECK(hipMemcpyAsync(&h, total, 4, hipMemcpyDeviceToHost, s));
+    ROGTK_HIP_CHECK(hipStreamSynchronize(s));
+    *n_out = (int64_t)h;
+    return ROGTK_OK;
+}
+
 template <int OW>
 int run_merge(const void* offs, const uint8_t* vals, const int64_t* rows, int64_t n, int64_t max_len, int L,
               int64_t n_reg, const CodeLookup* lookup, uint32_t* relabel, int64_t relabel_n, uint32_t* cluster_id,
@@ -452,6 +533,21 @@ int irregular_cluster(const void* offsets, int offset_width, const uint8_t* valu
     if (offset_width == 4)
         return run_exact<4>(offsets, values, rows, n_rows, max_len, stats_dev, cluster_id, n_irregular_clusters, s);
     return run_exact<8>(offsets, values, rows, n_rows, max_len, stats_dev, cluster_id, n_irregular_clusters, s);
+}
+
+int irregular_cluster_grouped(const void* offsets, int offset_width, const uint8_t* values, const int64_t* rows,
+                              int64_t n_rows, int64_t max_len, const uint32_t* groups, uint32_t max_group,
+                              uint32_t id_base, uint32_t* cluster_id, uint32_t* cluster_group,
+                              int64_t* n_irregular_clusters, hipStream_t s) {
+    *n_irregular_clusters = 0;
+    if (n_rows <= 0) return ROGTK_OK;
+    ROGTK_REQUIRE(n_rows < (1ll << 31), ROGTK_E_UNSUPPORTED, "irregular rows: more than 2^31");
+    ProfScope prof(K_IRREGULAR, s);
+    if (offset_width == 4)
+        return run_exact_grouped<4>(offsets, values, rows, n_rows, max_len, groups, max_group, id_base, cluster_id,
+                                    cluster_group, n_irregular_clusters, s);
+    return run_exact_grouped<8>(offsets, values, rows, n_rows, max_len, groups, max_group, id_base, cluster_id,
+                                cluster_group, n_irregular_clusters, s);
 }
 
 int irregular_merge(const void* offsets, int offset_width, const uint8_t* values, const int64_t* rows,

@@ -1060,8 +1060,49 @@ struct U32ResultHolder {
     rogtk_u32_result r{};
     ~U32ResultHolder() { rogtk_u32_result_free(&r); }
 };
+// The group keys of umi_correct_expr's second input: an integer series of any
+// width and sign, every chunk in order, as u32. Nulls, negative values and values above
+// 2^32 - 1 fail with a message.
+template <class T>
+void append_keys(const ArrowArray* a, std::vector<uint32_t>* keys) {
+    const T* v = (const T*)a->buffers[1] + a->offset;
+    for (int64_t r = 0; r < a->length; ++r) {
+        const T x = v[r];
+        if (std::is_signed<T>::value && x < 0) fail("group keys must be >= 0, got %lld", (long long)x);
+        if ((uint64_t)x > 0xFFFFFFFFull) fail("group keys must be <= 4294967295, got %llu", (unsigned long long)x);
+        keys->push_back((uint32_t)x);
+    }
+}
+std::vector<uint32_t> group_keys(const SeriesExport& s) {
+    if (!s.field || !s.field->format) fail("groups series has no field");
+    const std::string fmt = s.field->format;
+    std::vector<uint32_t> keys;
+    for (size_t c = 0; c < s.len; ++c) {
+        const ArrowArray* a = s.arrays[c];
+        int64_t nulls = a->null_count;
+        if (nulls < 0) {  // not counted by the producer
+            nulls = 0;
+            const uint8_t* vb = (const uint8_t*)a->buffers[0];
+            for (int64_t r = 0; vb && r < a->length; ++r) nulls += !((vb[(a->offset + r) >> 3] >> ((a->offset + r) & 7)) & 1);
+        }
+        if (nulls != 0) fail("the groups series has nulls; every row needs a key");
+        if (a->length == 0) continue;
+        if (fmt == "c") append_keys<int8_t>(a, &keys);
+        else if (fmt == "C") append_keys<uint8_t>(a, &keys);
+        else if (fmt == "s") append_keys<int16_t>(a, &keys);
+        else if (fmt == "S") append_keys<uint16_t>(a, &keys);
+        else if (fmt == "i") append_keys<int32_t>(a, &keys);
+        else if (fmt == "I") append_keys<uint32_t>(a, &keys);
+        else if (fmt == "l") append_keys<int64_t>(a, &keys);
+        else if (fmt == "L") append_keys<uint64_t>(a, &keys);
+        else fail("invalid groups dtype: expected an integer series, got `%s`", dtype_name(fmt.c_str()).c_str());
+    }
+    return keys;
+}
+
 void umi_correct_expr(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out) {
     if (n_in < 1) fail("expected one input series");
+    if (n_in > 2) fail("expected at most two input series (the UMIs and the group keys)");
     const int64_t umi_len = kw.opt_uint("umi_len", 0), maxd = kw.opt_uint("max_distance", 1);
     if (umi_len > (1 << 30) || maxd > (1 << 30)) fail("could not parse kwargs: umi_len / max_distance out of range");
     std::string method = "cluster";  // "directional" = the count-aware rule
@@ -1076,9 +1117,19 @@ void umi_correct_expr(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExp
     StrResultHolder corrected, reps;
     U32ResultHolder n_reads, n_distinct;
     int64_t n_clusters = 0;
-    check((directional ? rogtk_umi_correct_directional_host : rogtk_umi_correct_host)(
-        &d, (int)umi_len, (int)maxd, ids.data(), &corrected.r, &reps.r, &n_reads.r, &n_distinct.r, &n_clusters,
-        nullptr));
+    if (n_in == 2) {  // the grouped call: what replaces .over(group)
+        std::vector<uint32_t> keys = group_keys(in[1]);
+        if ((int64_t)keys.size() != f.n)
+            fail("the groups series has %lld rows, the UMI series has %lld", (long long)keys.size(), (long long)f.n);
+        if (keys.empty()) keys.push_back(0);
+        check(rogtk_umi_correct_grouped_host(&d, keys.data(), (int)umi_len, directional ? 1 : 0, (int)maxd, ids.data(),
+                                             &corrected.r, &reps.r, &n_reads.r, &n_distinct.r, nullptr, &n_clusters,
+                                             nullptr));
+    } else {
+        check((directional ? rogtk_umi_correct_directional_host : rogtk_umi_correct_host)(
+            &d, (int)umi_len, (int)maxd, ids.data(), &corrected.r, &reps.r, &n_reads.r, &n_distinct.r, &n_clusters,
+            nullptr));
+    }
     std::vector<Col> chunks;
     chunks.push_back(view_col_result(corrected.r));
     export_series(out, {s.name, "vu", {}}, std::move(chunks));

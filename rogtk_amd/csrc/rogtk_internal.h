@@ -399,9 +399,13 @@ int cc_labels(int64_t nv, const uint32_t* edges, int64_t m, uint32_t* labels, in
 // own (each one is a real allocation and release; profiles/refactor_sort_engines.json).
 struct SortedCodes;
 using ExtraCodeBytes = std::function<int(int64_t m, size_t* bytes)>;
+// groups (nullable, device, one u32 key per row): D holds the composites
+// key << 2 L | code of the regular rows, sorted over exactly 2 L + bit_width(largest key) bits
+// (out->key_bits; ROGTK_E_UNSUPPORTED past 64, seen after the pack kernel's read-back), and
+// out->max_group / max_irr_group are the largest keys of the regular / irregular rows.
 int sorted_distinct_codes(const void* offsets, int ow, const uint8_t* values, const uint8_t* validity, int64_t voff,
                           int64_t n, int L, bool want_counts, const ExtraCodeBytes* extra, uint32_t* cluster_id,
-                          SortedCodes* out, hipStream_t s);
+                          SortedCodes* out, hipStream_t s, const uint32_t* groups = nullptr);
 
 // H3 for 17 <= L <= 32 (sort-based, long_cluster.hip): regular + irregular rows of a
 // device column; ids into cid (device), *n_clusters on the host. Synchronises s.
@@ -440,9 +444,21 @@ int corrected_fill(const void* offsets, int ow, const uint8_t* values, const uin
 // D[m] ascending distinct codes, C[m] their row counts (device): root[m] (index into D),
 // labels[m] (dense, ascending in the root's code), *n_clusters and *rounds on the host.
 // Synchronises s. ROGTK_E_HIP when the relaxation has no fixed point after m rounds.
+// grp (nullable): D holds composites key << shift | code, and the edge search of
+// a code stays inside the entries of its own key (window: kWindow*).
+enum { kWindowValue = 0, kWindowTable = 1, kWindowGallop = 2 };
+struct DirGroups {
+    int shift;               // 2 L: the composite's key starts at this bit (64: every key is 0)
+    int window;              // kWindowValue: the ungrouped bound by value distance alone;
+                             // kWindowTable: clamped to gstart[gidx[v]] .. gstart[gidx[v] + 1];
+                             // kWindowGallop: clamped to a range found by galloping out from v
+    const uint32_t* gidx;    // [m] rank of the code's key among the distinct keys (table only)
+    const uint32_t* gstart;  // [distinct keys + 1] first index in D of every key, then m
+};
 int directional_codes_temp(int64_t m, int L, int64_t* bytes);
 int directional_codes(const uint64_t* D, const uint32_t* C, int64_t m, int L, uint32_t* root, uint32_t* labels,
-                      int64_t* n_clusters, int64_t* rounds, void* temp, int64_t temp_bytes, hipStream_t s);
+                      int64_t* n_clusters, int64_t* rounds, void* temp, int64_t temp_bytes, hipStream_t s,
+                      const DirGroups* grp = nullptr);
 // a device string column: ids into cluster_id[n] (regular clusters, then the irregular strings
 // by exact bytes; 0xFFFFFFFF for null rows), root_code[n] (nullable: the code of the row's
 // root, all ones for a row that is not regular); *longest (nullable) = the byte length of the
@@ -450,5 +466,22 @@ int directional_codes(const uint64_t* D, const uint32_t* C, int64_t m, int L, ui
 int directional_cluster(const void* offsets, int ow, const uint8_t* values, const uint8_t* validity, int64_t voff,
                         int64_t n, int L, uint32_t* cluster_id, uint64_t* root_code, int64_t* n_clusters,
                         int64_t* rounds, int64_t* longest, hipStream_t s);
+
+// ------------------------------------- grouped UMI clustering (grouped.hip)
+// As directional_cluster with one u32 key per row (groups, device): two rows share a cluster
+// only under equal keys. max_distance 1: the directional rule per key; 0: the distinct (key,
+// string) pairs. cluster_group[n] (nullable, device): the key of every cluster. Synchronises s.
+int grouped_cluster(const void* offsets, int ow, const uint8_t* values, const uint8_t* validity, int64_t voff,
+                    int64_t n, int L, const uint32_t* groups, int max_distance, uint32_t* cluster_id,
+                    uint64_t* root_code, uint32_t* cluster_group, int64_t* n_clusters, int64_t* rounds,
+                    int64_t* longest, hipStream_t s);
+// how the grouped edge search finds its window (kWindow*; measurements only)
+int grouped_set_window(int window);
+// irregular rows as the distinct (key, bytes) pairs in that order (irregular.hip): ids from
+// id_base on, cluster_group[id] = key (nullable). max_group: the largest key among the rows.
+int irregular_cluster_grouped(const void* offsets, int offset_width, const uint8_t* values, const int64_t* rows,
+                              int64_t n_rows, int64_t max_len, const uint32_t* groups, uint32_t max_group,
+                              uint32_t id_base, uint32_t* cluster_id, uint32_t* cluster_group,
+                              int64_t* n_irregular_clusters, hipStream_t s);
 
 }  // namespace rogtk

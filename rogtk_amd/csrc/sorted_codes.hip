@@ -7,6 +7,10 @@
 //            classifies kPackTile rows and reserves its two ranges with one atomic each.
 //   sort     radix sort of the pairs over the 2 L code bits (u32 keys for L <= 16, u64 above;
 //            u32 row payloads: n < 2^31).
+//   groups    with one u32 key per row the pack kernel builds the u64 composite
+//            key << 2 L | code and records the largest key of the regular and of the irregular
+//            rows; the sort then runs over exactly 2 L + bit_width(largest key) bits and D
+//            holds composites. A template parameter: the ungrouped kernels are unchanged.
 //   distinct flag every sorted row whose code differs from its predecessor's; the inclusive
 //            scan of the flags is the row's index into the distinct codes D, and the heads of
 //            the runs write D (and, when counts are wanted, their positions: C[j] is the
@@ -25,14 +29,18 @@ constexpr int kBlock = 256;
 constexpr int kPackRows = 4;  // rows per thread of k_pack
 constexpr int kPackTile = kBlock * kPackRows;
 
-// cnt[0] regular rows, cnt[1] irregular rows, cnt[2] the longest irregular row
-template <int OW, class K>
+// cnt[0] regular rows, cnt[1] irregular rows, cnt[2] the longest irregular row; GROUPED: the
+// two u32 halves of cnt[3] are the largest key of a regular and of an irregular row
+template <int OW, class K, bool GROUPED>
 __global__ void __launch_bounds__(kBlock)
 k_pack(const void* __restrict__ offs, const uint8_t* __restrict__ vals, const uint8_t* __restrict__ validity,
        int64_t voff, int64_t n, int L, K* __restrict__ key, uint32_t* __restrict__ row, int64_t* __restrict__ irr,
-       uint32_t* __restrict__ cluster_id, unsigned long long* __restrict__ cnt) {
+       uint32_t* __restrict__ cluster_id, unsigned long long* __restrict__ cnt,
+       const uint32_t* __restrict__ groups) {
     constexpr int kWaves = kBlock / 64;
     __shared__ uint32_t pre_r[kPackRows * kWaves], pre_i[kPackRows * kWaves];
+    [[maybe_unused]] __shared__ uint32_t gmax[2 * kWaves];
+    [[maybe_unused]] uint32_t gmax_r = 0, gmax_i = 0;
     __shared__ unsigned long long base[2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t tile = (int64_t)blockIdx.x * kPackTile;
@@ -54,6 +62,15 @@ k_pack(const void* __restrict__ offs, const uint8_t* __restrict__ vals, const ui
                     c = (c << 2) | (uint64_t)(b & 3);
                 }
                 if (!regular) longest = max(longest, (unsigned long long)len);
+                if constexpr (GROUPED) {
+                    const uint32_t g = groups[i];
+                    if (regular) {
+                        gmax_r = max(gmax_r, g);
+                        if (L < 32) c |= (uint64_t)g << (2 * L);  // L == 32: only key 0 fits (checked on the host)
+                    } else {
+                        gmax_i = max(gmax_i, g);
+                    }
+                }
             } else {
                 cluster_id[i] = 0xFFFFFFFFu;
             }
@@ -68,7 +85,24 @@ k_pack(const void* __restrict__ offs, const uint8_t* __restrict__ vals, const ui
     }
     for (int d = 32; d; d >>= 1) longest = max(longest, (unsigned long long)__shfl_xor(longest, d));
     if (lane == 0 && longest) atomicMax(&cnt[2], longest);
+    if constexpr (GROUPED) {
+        for (int d = 32; d; d >>= 1) {
+            gmax_r = max(gmax_r, (uint32_t)__shfl_xor(gmax_r, d));
+            gmax_i = max(gmax_i, (uint32_t)__shfl_xor(gmax_i, d));
+        }
+        if (lane == 0) {
+            gmax[wave] = gmax_r;
+            gmax[kWaves + wave] = gmax_i;
+        }
+    }
     __syncthreads();
+    if constexpr (GROUPED) {
+        if (threadIdx.x < 2) {  // one atomic per workgroup and kind
+            uint32_t g = 0;
+            for (int w = 0; w < kWaves; ++w) g = max(g, gmax[threadIdx.x * kWaves + w]);
+            if (g) atomicMax((uint32_t*)(cnt + 3) + threadIdx.x, g);
+        }
+    }
     if (threadIdx.x == 0) {
         uint32_t sr = 0, si = 0;
         for (int k = 0; k < kPackRows * kWaves; ++k) {
@@ -120,15 +154,17 @@ __global__ void k_counts(const uint32_t* __restrict__ head, int64_t m, int64_t n
     C[j] = (j + 1 < m ? head[j + 1] : (uint32_t)n) - head[j];
 }
 
-template <int OW, class K>
+template <int OW, class K, bool GROUPED>
 int run(const void* offs, const uint8_t* vals, const uint8_t* validity, int64_t voff, int64_t n, int L,
-        bool want_counts, const ExtraCodeBytes* extra, uint32_t* cluster_id, SortedCodes* out, hipStream_t s) {
+        bool want_counts, const ExtraCodeBytes* extra, uint32_t* cluster_id, SortedCodes* out, hipStream_t s,
+        const uint32_t* groups) {
     const dim3 b(kBlock);
-    const int bits = L >= 1 && L <= 32 ? 2 * L : 2;  // any other L: no row is regular
+    int bits = L >= 1 && L <= 32 ? 2 * L : 2;  // any other L: no row is regular
     size_t sort_b = 0, scan_b = 0;
+    // (sized for the widest key the grouped sort can run over)
     ROGTK_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_b, (const K*)nullptr, (K*)nullptr,
-                                                       (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, bits,
-                                                       s));
+                                                       (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0,
+                                                       GROUPED ? 64 : bits, s));
     ROGTK_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(nullptr, scan_b, (const uint32_t*)nullptr, (uint32_t*)nullptr,
                                                      (int)n, s));
     const size_t tmp_b = std::max(sort_b, scan_b);
@@ -146,12 +182,23 @@ int run(const void* offs, const uint8_t* vals, const uint8_t* validity, int64_t 
     int64_t* irr = A.take<int64_t>(n);
     void* tmp = A.take<uint8_t>((int64_t)tmp_b);
     ROGTK_HIP_CHECK(hipMemsetAsync(cnt, 0, 64, s));
-    hipLaunchKernelGGL((k_pack<OW, K>), dim3(grid_for(n, kPackTile)), b, 0, s, offs, vals, validity, voff, n, L, key,
-                       row, irr, cluster_id, cnt);
+    hipLaunchKernelGGL((k_pack<OW, K, GROUPED>), dim3(grid_for(n, kPackTile)), b, 0, s, offs, vals, validity, voff, n,
+                       L, key, row, irr, cluster_id, cnt, groups);
     ROGTK_HIP_CHECK(hipGetLastError());
-    unsigned long long h[3];
-    ROGTK_HIP_CHECK(hipMemcpyAsync(h, cnt, 24, hipMemcpyDeviceToHost, s));
+    unsigned long long h[4];
+    ROGTK_HIP_CHECK(hipMemcpyAsync(h, cnt, 32, hipMemcpyDeviceToHost, s));
     ROGTK_HIP_CHECK(hipStreamSynchronize(s));
+    if (GROUPED) {
+        out->max_group = (uint32_t)h[3];
+        out->max_irr_group = (uint32_t)(h[3] >> 32);
+        int gb = 0;
+        while (gb < 32 && (out->max_group >> gb)) ++gb;
+        ROGTK_REQUIRE(h[0] == 0 || bits + gb <= 64, ROGTK_E_UNSUPPORTED,
+                      "grouped: umi_len %d with a group key of %d bits needs a %d-bit sort key (at most 64)", L, gb,
+                      bits + gb);
+        bits += gb;
+    }
+    out->key_bits = bits;
     const int64_t n_reg = (int64_t)h[0];
     out->n_reg = n_reg;
     out->n_irr = (int64_t)h[1];
@@ -192,15 +239,20 @@ int run(const void* offs, const uint8_t* vals, const uint8_t* validity, int64_t 
 
 int sorted_distinct_codes(const void* offsets, int ow, const uint8_t* values, const uint8_t* validity, int64_t voff,
                           int64_t n, int L, bool want_counts, const ExtraCodeBytes* extra, uint32_t* cluster_id,
-                          SortedCodes* out, hipStream_t s) {
+                          SortedCodes* out, hipStream_t s, const uint32_t* groups) {
     ROGTK_REQUIRE(n > 0 && n < (1ll << 31), ROGTK_E_UNSUPPORTED, "sorted codes: n %lld outside 1..2^31-1",
                   (long long)n);
+    auto go = [&](auto ow_tag, auto key_tag, auto grouped_tag) {
+        return run<decltype(ow_tag)::value, decltype(key_tag), decltype(grouped_tag)::value>(
+            offsets, values, validity, voff, n, L, want_counts, extra, cluster_id, out, s, groups);
+    };
+    using W4 = std::integral_constant<int, 4>;
+    using W8 = std::integral_constant<int, 8>;
+    if (groups)  // composites are u64 whatever L
+        return ow == 4 ? go(W4{}, uint64_t{}, std::true_type{}) : go(W8{}, uint64_t{}, std::true_type{});
     const bool wide = L > 16;
-    if (ow == 4)
-        return wide ? run<4, uint64_t>(offsets, values, validity, voff, n, L, want_counts, extra, cluster_id, out, s)
-                    : run<4, uint32_t>(offsets, values, validity, voff, n, L, want_counts, extra, cluster_id, out, s);
-    return wide ? run<8, uint64_t>(offsets, values, validity, voff, n, L, want_counts, extra, cluster_id, out, s)
-                : run<8, uint32_t>(offsets, values, validity, voff, n, L, want_counts, extra, cluster_id, out, s);
+    if (ow == 4) return wide ? go(W4{}, uint64_t{}, std::false_type{}) : go(W4{}, uint32_t{}, std::false_type{});
+    return wide ? go(W8{}, uint64_t{}, std::false_type{}) : go(W8{}, uint32_t{}, std::false_type{});
 }
 
 }  // namespace rogtk

@@ -285,9 +285,12 @@ def register_polars():
         def dust_score(self):
             return reg("umi_dust_score_expr", self._expr, is_elementwise=True)
 
-        def correct(self, umi_len: int = 0, max_distance: int = 1, method: str = "cluster"):
-            # not elementwise: a row's corrected UMI depends on the whole column
-            return reg("umi_correct_expr", self._expr,
+        def correct(self, umi_len: int = 0, max_distance: int = 1, method: str = "cluster", groups=None):
+            # not elementwise: a row's corrected UMI depends on the whole column.
+            # groups (an integer expression): correction within each key in one
+            # call, the route that replaces .over(group)
+            args = self._expr if groups is None else [self._expr, groups]
+            return reg("umi_correct_expr", args,
                        {"umi_len": umi_len, "max_distance": max_distance, "method": method}, is_elementwise=False)
 
     def umi_complexity_scores(expr):  # :493-526
