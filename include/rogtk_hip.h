@@ -791,6 +791,59 @@ int rogtk_umi_correct_grouped_host(const rogtk_str_col* col, const uint32_t* gro
  * default). The answers are the same. */
 int rogtk_grouped_set_window(int window);
 
+/* ====== Cell-barcode correction against a whitelist (barcode.hip; spec: DESIGN.md §4e) ======
+ * The whitelist: W >= 1 distinct strings of one byte length L (1..32) over the bytes A C G T,
+ * W < 2^32 - 1; the row number in the caller's order is the barcode's index. Anything else is
+ * ROGTK_E_INVALID and the message names the first offending row.
+ * Per row, a position is unknown when its byte is not one of ACGT. A null row has status
+ * null; a row of another byte length or with two or more unknown positions has no candidates;
+ * a row without unknown positions that is in the whitelist is exact; otherwise its candidates
+ * are the whitelist entries at Hamming distance exactly 1 (no unknown position) or those that
+ * agree at the L - 1 known positions (one unknown position). No candidate: no_match; one:
+ * corrected to it; two or more: ambiguous under ROGTK_BC_REJECT, under ROGTK_BC_COUNTS the
+ * candidate whose prior count is strictly the largest (a tie at the top: ambiguous). The prior
+ * count of entry w is prior_counts[w] when given, else the exact rows of w in this call.
+ * index[i]: the whitelist index for status exact / corrected, 0xFFFFFFFF otherwise.
+ * exact_counts[W] / counts[W]: the rows of every entry that are exact / exact or corrected.
+ * totals5: the rows per status, in the order of the status values. n < 2^31. Nothing depends on
+ * row order, chunking or entry point. */
+#define ROGTK_BC_EXACT 0
+#define ROGTK_BC_CORRECTED 1
+#define ROGTK_BC_AMBIGUOUS 2
+#define ROGTK_BC_NO_MATCH 3
+#define ROGTK_BC_NULL 4
+#define ROGTK_BC_COUNTS 0 /* ambiguous = */
+#define ROGTK_BC_REJECT 1
+/* The handle of a HOST whitelist column: immutable, bound to the device current at creation,
+ * reusable across calls, batches and streams (the scratch of a call is its own). */
+int rogtk_barcode_whitelist_create(const rogtk_str_col* whitelist, void** out);
+void rogtk_barcode_whitelist_free(void* handle);
+/* prefix_digits: the P of the direct-address table start[4^P + 1]; device_bytes: what the handle holds */
+int rogtk_barcode_whitelist_info(const void* handle, int64_t* W, int* L, int* prefix_digits, int64_t* device_bytes);
+/* Device column (layout as rogtk_umi_cluster_dev); prior_counts (nullable), index[n], status[n],
+ * exact_counts (nullable, [W]) and counts (nullable, [W]) on the device, totals5 on the host.
+ * Synchronises `stream`. */
+int rogtk_barcode_correct_dev(const void* handle, const int64_t* offsets, const uint8_t* values,
+                              const uint8_t* validity, int64_t n, int ambiguous, const uint32_t* prior_counts,
+                              uint32_t* index, uint8_t* status, uint32_t* exact_counts, uint32_t* counts,
+                              int64_t* totals5, void* stream);
+/* Host column and outputs; corrected (nullable): the whitelist string of the rows with status
+ * exact / corrected, null otherwise (rogtk_str_result_free). */
+int rogtk_barcode_correct_host(const void* handle, const rogtk_str_col* col, int ambiguous,
+                               const uint32_t* prior_counts, uint32_t* index, uint8_t* status,
+                               rogtk_str_result* corrected, uint32_t* exact_counts, uint32_t* counts,
+                               int64_t* totals5);
+/* The exact pass alone, ADDING into the caller's exact_counts[W] (a file read in batches is
+ * counted first and corrected second with prior_counts = the whole file's counts). totals5
+ * (nullable): exact, null and candidate-less rows (the latter under no_match). */
+int rogtk_barcode_count_dev(const void* handle, const int64_t* offsets, const uint8_t* values,
+                            const uint8_t* validity, int64_t n, uint32_t* exact_counts, int64_t* totals5, void* stream);
+int rogtk_barcode_count_host(const void* handle, const rogtk_str_col* col, uint32_t* exact_counts, int64_t* totals5);
+/* Measurements only (process-wide): 0 a wave per miss, 1 a lane per miss (the default); + 2:
+ * lookups by a binary search over the whole whitelist instead of the prefix table. The answers
+ * are the same. */
+int rogtk_barcode_set_probe(int probe);
+
 /* ============================== profiling ================================ */
 /* When enabled, every kernel launch is bracketed by HIP events on its stream. */
 /* ======== multi-GPU exchange of read groups ========

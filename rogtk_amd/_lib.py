@@ -244,6 +244,15 @@ SIGNATURES = {
                                        ctypes.POINTER(StrResult), ctypes.POINTER(U32Result),
                                        ctypes.POINTER(U32Result), ctypes.POINTER(U32Result), _P_I64, _P_I32],
     "rogtk_grouped_set_window": [_i32],
+    # cell-barcode correction
+    "rogtk_barcode_whitelist_create": [ctypes.POINTER(StrCol), ctypes.POINTER(ctypes.c_void_p)],
+    "rogtk_barcode_whitelist_info": [_vp, _P_I64, _P_I32, _P_I32, _P_I64],
+    "rogtk_barcode_correct_dev": [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _P_I64, _vp],
+    "rogtk_barcode_correct_host": [_vp, ctypes.POINTER(StrCol), _i32, _vp, _vp, _vp, ctypes.POINTER(StrResult), _vp,
+                                   _vp, _P_I64],
+    "rogtk_barcode_count_dev": [_vp, _vp, _vp, _vp, _i64, _vp, _P_I64, _vp],
+    "rogtk_barcode_count_host": [_vp, ctypes.POINTER(StrCol), _vp, _P_I64],
+    "rogtk_barcode_set_probe": [_i32],
     "rogtk_profile_enable": [_i32],
     "rogtk_profile_select": [ctypes.c_char_p],
     "rogtk_profile_reset": [],
@@ -256,6 +265,7 @@ VOID_SIGNATURES = {
     "rogtk_str_result_free": [ctypes.POINTER(StrResult)],
     "rogtk_fuzzy_free": [_vp],
     "rogtk_u32_result_free": [ctypes.POINTER(U32Result)],
+    "rogtk_barcode_whitelist_free": [_vp],
 }
 
 _lock = threading.Lock()

@@ -373,6 +373,9 @@ class Col:
         self.dna = DnaNamespace(column)
         self.cigar = CigarNamespace(column)
         self.fuzzy = FuzzyNamespace(column)
+        from .barcode import BarcodeNamespace
+
+        self.barcode = BarcodeNamespace(column)
 
 
 def col(column: ColumnLike) -> Col:

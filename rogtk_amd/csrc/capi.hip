@@ -1735,6 +1735,193 @@ int rogtk_umi_correct_grouped_host(const rogtk_str_col* col, const uint32_t* gro
                         n_clusters, resolved_umi_len, groups ? groups : &no_rows, cluster_group);
 }
 
+// ------------------------------------ cell-barcode correction (barcode.hip)
+int rogtk_barcode_set_probe(int probe) { return barcode_set_probe(probe); }
+
+int rogtk_barcode_whitelist_create(const rogtk_str_col* wl, void** out) {
+    ROGTK_REQUIRE(wl && out, ROGTK_E_INVALID, "barcode whitelist: NULL argument");
+    *out = nullptr;
+    HostCol h{wl->offsets, wl->offset_width, wl->values, wl->values_len, wl->validity, wl->validity_offset, wl->n};
+    if (int rc = check_host_col(h)) return rc;
+    const int64_t W = h.n;
+    ROGTK_REQUIRE(W >= 1, ROGTK_E_INVALID, "barcode whitelist: empty");
+    ROGTK_REQUIRE(W < (1ll << 32) - 1, ROGTK_E_INVALID, "barcode whitelist: %lld rows, at most 2^32 - 2", (long long)W);
+    ROGTK_REQUIRE(h.valid(0), ROGTK_E_INVALID, "barcode whitelist: row 0 is null");
+    const int64_t L = h.off(1) - h.off(0);
+    ROGTK_REQUIRE(L >= 1 && L <= 32, ROGTK_E_INVALID, "barcode whitelist: row 0 has %lld bytes, outside 1..32",
+                  (long long)L);
+    std::vector<uint64_t> codes((size_t)W);
+    for (int64_t i = 0; i < W; ++i) {
+        ROGTK_REQUIRE(h.valid(i), ROGTK_E_INVALID, "barcode whitelist: row %lld is null", (long long)i);
+        ROGTK_REQUIRE(h.off(i + 1) - h.off(i) == L, ROGTK_E_INVALID,
+                      "barcode whitelist: row %lld has %lld bytes, row 0 has %lld", (long long)i,
+                      (long long)(h.off(i + 1) - h.off(i)), (long long)L);
+        uint64_t c = 0;
+        for (int64_t j = 0; j < L; ++j) {
+            const uint8_t ch = h.values[h.off(i) + j];
+            const int b = ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : -1;
+            ROGTK_REQUIRE(b >= 0, ROGTK_E_INVALID, "barcode whitelist: row %lld has byte 0x%02x at position %lld (only ACGT)",
+                          (long long)i, ch, (long long)j);
+            c = (c << 2) | (uint64_t)b;
+        }
+        codes[(size_t)i] = c;
+    }
+    HostCtx* c;
+    if (int rc = host_ctx(&c)) return rc;
+    return barcode_whitelist_build(codes.data(), W, (int)L, out, c->stream);
+}
+
+void rogtk_barcode_whitelist_free(void* handle) { barcode_whitelist_free(handle); }
+
+int rogtk_barcode_whitelist_info(const void* handle, int64_t* W, int* L, int* prefix_digits, int64_t* device_bytes) {
+    return barcode_whitelist_info(handle, W, L, prefix_digits, device_bytes);
+}
+
+namespace {
+
+static int check_barcode(const char* name, const void* handle, int64_t n, int ambiguous, int64_t* W) {
+    ROGTK_REQUIRE(handle, ROGTK_E_INVALID, "%s: NULL whitelist handle", name);
+    ROGTK_REQUIRE(n >= 0 && n < (1ll << 31), ROGTK_E_UNSUPPORTED, "%s: n %lld outside 0..2^31-1", name, (long long)n);
+    ROGTK_REQUIRE(ambiguous == ROGTK_BC_COUNTS || ambiguous == ROGTK_BC_REJECT, ROGTK_E_INVALID,
+                  "%s: ambiguous %d is neither 0 (counts) nor 1 (reject)", name, ambiguous);
+    return barcode_whitelist_info(handle, W, nullptr, nullptr, nullptr);
+}
+
+// the offsets, values and validity of a host column on the context's buffers (no staging pass)
+static int upload_col(HostCtx* c, const HostCol& h) {
+    const int64_t n = h.n;
+    ROGTK_REQUIRE(h.off(n) <= h.values_len || h.values_len < 0, ROGTK_E_INVALID,
+                  "offsets reference %lld bytes but values_len is %lld", (long long)h.off(n), (long long)h.values_len);
+    if (int rc = c->offsets.ensure((size_t)(n + 1) * h.ow)) return rc;
+    if (int rc = c->h2d(c->offsets.p, h.offsets, (size_t)(n + 1) * h.ow)) return rc;
+    if (int rc = c->values.ensure((size_t)std::max<int64_t>(h.off(n), 1))) return rc;
+    if (int rc = c->h2d(c->values.p, h.values, (size_t)h.off(n))) return rc;
+    if (h.validity) {
+        const size_t vb = (size_t)((h.voff + n + 7) / 8);
+        if (int rc = c->validity.ensure(vb)) return rc;
+        if (int rc = c->h2d(c->validity.p, h.validity, vb)) return rc;
+    }
+    return ROGTK_OK;
+}
+
+}  // namespace
+
+int rogtk_barcode_correct_dev(const void* handle, const int64_t* offsets, const uint8_t* values,
+                              const uint8_t* validity, int64_t n, int ambiguous, const uint32_t* prior_counts,
+                              uint32_t* index, uint8_t* status, uint32_t* exact_counts, uint32_t* counts,
+                              int64_t* totals5, void* stream) {
+    int64_t W = 0;
+    if (int rc = check_barcode("barcode_correct_dev", handle, n, ambiguous, &W)) return rc;
+    ROGTK_REQUIRE(n == 0 || (offsets && values && index && status), ROGTK_E_INVALID,
+                  "barcode_correct_dev: NULL argument");
+    static uint32_t no_index;  // an empty column still runs the correcting path
+    static uint8_t no_status;
+    return barcode_correct(handle, offsets, 8, values, validity, 0, n, ambiguous, prior_counts,
+                           index ? index : &no_index, status ? status : &no_status, exact_counts, counts, false,
+                           totals5, as_stream(stream));
+}
+
+int rogtk_barcode_count_dev(const void* handle, const int64_t* offsets, const uint8_t* values,
+                            const uint8_t* validity, int64_t n, uint32_t* exact_counts, int64_t* totals5,
+                            void* stream) {
+    int64_t W = 0;
+    if (int rc = check_barcode("barcode_count_dev", handle, n, ROGTK_BC_COUNTS, &W)) return rc;
+    ROGTK_REQUIRE(exact_counts && (n == 0 || (offsets && values)), ROGTK_E_INVALID, "barcode_count_dev: NULL argument");
+    return barcode_correct(handle, offsets, 8, values, validity, 0, n, ROGTK_BC_COUNTS, nullptr, nullptr, nullptr,
+                           exact_counts, nullptr, true, totals5, as_stream(stream));
+}
+
+int rogtk_barcode_count_host(const void* handle, const rogtk_str_col* col, uint32_t* exact_counts, int64_t* totals5) {
+    ROGTK_REQUIRE(col && exact_counts, ROGTK_E_INVALID, "barcode_count: NULL argument");
+    int64_t W = 0;
+    if (int rc = check_barcode("barcode_count", handle, col->n, ROGTK_BC_COUNTS, &W)) return rc;
+    HostCol h{col->offsets, col->offset_width, col->values, col->values_len, col->validity, col->validity_offset,
+              col->n};
+    if (int rc = check_host_col(h)) return rc;
+    HostCtx* c;
+    if (int rc = host_ctx(&c)) return rc;
+    if (int rc = upload_col(c, h)) return rc;
+    if (int rc = c->out[1].ensure((size_t)W * 4)) return rc;
+    if (int rc = c->h2d(c->out[1].p, exact_counts, (size_t)W * 4)) return rc;
+    if (int rc = barcode_correct(handle, c->offsets.p, h.ow, c->values.as<uint8_t>(),
+                                 h.validity ? c->validity.as<uint8_t>() : nullptr, h.voff, h.n, ROGTK_BC_COUNTS, nullptr,
+                                 nullptr, nullptr, c->out[1].as<uint32_t>(), nullptr, true, totals5, c->stream))
+        return rc;
+    return c->d2h(exact_counts, c->out[1].p, (size_t)W * 4);
+}
+
+int rogtk_barcode_correct_host(const void* handle, const rogtk_str_col* col, int ambiguous,
+                               const uint32_t* prior_counts, uint32_t* index, uint8_t* status,
+                               rogtk_str_result* corrected, uint32_t* exact_counts, uint32_t* counts,
+                               int64_t* totals5) {
+    if (corrected) *corrected = rogtk_str_result{};
+    ROGTK_REQUIRE(col, ROGTK_E_INVALID, "barcode_correct: NULL column");
+    int64_t W = 0;
+    if (int rc = check_barcode("barcode_correct", handle, col->n, ambiguous, &W)) return rc;
+    HostCol h{col->offsets, col->offset_width, col->values, col->values_len, col->validity, col->validity_offset,
+              col->n};
+    if (int rc = check_host_col(h)) return rc;
+    const int64_t n = h.n;
+    ROGTK_REQUIRE(n == 0 || (index && status), ROGTK_E_INVALID, "barcode_correct: index or status is NULL");
+    HostCtx* c;
+    if (int rc = host_ctx(&c)) return rc;
+    auto run = [&]() -> int {
+        if (int rc = upload_col(c, h)) return rc;
+        const int64_t n1 = std::max<int64_t>(n, 1);
+        if (c->out[0].ensure((size_t)n1 * 4) || c->out[1].ensure((size_t)W * 4) || c->out[2].ensure((size_t)W * 4) ||
+            c->out[3].ensure((size_t)W * 4) || c->out[7].ensure((size_t)n1))
+            return ROGTK_E_HIP;
+        uint32_t* d_index = c->out[0].as<uint32_t>();
+        uint8_t* d_status = c->out[7].as<uint8_t>();
+        if (prior_counts)
+            if (int rc = c->h2d(c->out[3].p, prior_counts, (size_t)W * 4)) return rc;
+        if (int rc = barcode_correct(handle, c->offsets.p, h.ow, c->values.as<uint8_t>(),
+                                     h.validity ? c->validity.as<uint8_t>() : nullptr, h.voff, n, ambiguous,
+                                     prior_counts ? c->out[3].as<uint32_t>() : nullptr, d_index, d_status,
+                                     c->out[1].as<uint32_t>(), c->out[2].as<uint32_t>(), false, totals5, c->stream))
+            return rc;
+        if (n > 0) {
+            if (int rc = c->d2h(index, d_index, (size_t)n * 4)) return rc;
+            if (int rc = c->d2h(status, d_status, (size_t)n)) return rc;
+        }
+        if (exact_counts)
+            if (int rc = c->d2h(exact_counts, c->out[1].p, (size_t)W * 4)) return rc;
+        if (counts)
+            if (int rc = c->d2h(counts, c->out[2].p, (size_t)W * 4)) return rc;
+        if (!corrected) return ROGTK_OK;
+        if (int rc = empty_str_result(n, corrected)) return rc;
+        for (int64_t i = 0; i < n; ++i) {
+            if (status[i] <= ROGTK_BC_CORRECTED) corrected->validity[i >> 3] |= (uint8_t)(1u << (i & 7));
+            else ++corrected->null_count;
+        }
+        if (n == 0) return ROGTK_OK;
+        int64_t tb = 0;
+        if (int rc = barcode_corrected_temp(n, &tb)) return rc;
+        if (c->out[4].ensure((size_t)(n + 1) * 8) || c->out[5].ensure((size_t)tb)) return ROGTK_E_HIP;
+        if (int rc = barcode_corrected_measure(handle, d_status, n, c->out[4].as<int64_t>(), c->out[5].p, tb,
+                                               c->stream))
+            return rc;
+        if (int rc = c->d2h(corrected->offsets, c->out[4].p, (size_t)(n + 1) * 8)) return rc;
+        const int64_t total = corrected->offsets[n];
+        if (total > 0) {
+            free(corrected->values);
+            corrected->values = (uint8_t*)malloc((size_t)total);
+            ROGTK_REQUIRE(corrected->values, ROGTK_E_INVALID, "out of host memory for %lld output bytes",
+                          (long long)total);
+            corrected->values_len = total;
+            if (c->out[6].ensure((size_t)total)) return ROGTK_E_HIP;
+            if (int rc = barcode_corrected_fill(handle, d_index, d_status, n, c->out[4].as<int64_t>(),
+                                                c->out[6].as<uint8_t>(), c->stream))
+                return rc;
+            if (int rc = c->d2h(corrected->values, c->out[6].p, (size_t)total)) return rc;
+        }
+        return ROGTK_OK;
+    };
+    const int rc = run();
+    if (rc && corrected) rogtk_str_result_free(corrected);
+    return rc;
+}
+
 // --------------------------------------------------------------- stream events
 int rogtk_event_create(int flags, void** out) {
     ROGTK_REQUIRE(out, ROGTK_E_INVALID, "event_create: NULL out");

@@ -1135,6 +1135,45 @@ void umi_correct_expr(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExp
     export_series(out, {s.name, "vu", {}}, std::move(chunks));
 }
 
+// ------------------------------------------------------- cell-barcode correction
+// barcode_correct_expr (no reference counterpart): input 0 the barcodes (every
+// chunk as ONE batch), input 1 the whitelist (a string series of any length) -> the whitelist
+// index of every row, null where the row is neither exact nor corrected. The whitelist handle
+// is built per call.
+struct BarcodeWhitelistHolder {
+    void* h = nullptr;
+    ~BarcodeWhitelistHolder() { rogtk_barcode_whitelist_free(h); }
+};
+void barcode_correct_expr(SeriesExport* in, size_t n_in, const Kwargs& kw, SeriesExport* out) {
+    if (n_in != 2) fail("expected two input series (the barcodes and the whitelist), got %zu", n_in);
+    std::string ambiguous = "counts";
+    kw.opt_str("ambiguous", &ambiguous);
+    if (ambiguous != "counts" && ambiguous != "reject")
+        fail("could not parse kwargs: unknown `ambiguous` \"%s\" (expected \"counts\" or \"reject\")", ambiguous.c_str());
+    StrSeries s = str_series(in[0]);
+    FlatCol wf = flatten_all(str_series(in[1]));
+    const rogtk_str_col wd = str_desc(wf);
+    BarcodeWhitelistHolder wl;
+    check(rogtk_barcode_whitelist_create(&wd, &wl.h));
+    FlatCol f = flatten_all(s);
+    const rogtk_str_col d = str_desc(f);
+    std::vector<uint32_t> index((size_t)std::max<int64_t>(f.n, 1));
+    std::vector<uint8_t> status((size_t)std::max<int64_t>(f.n, 1));
+    int64_t totals[5];
+    check(rogtk_barcode_correct_host(wl.h, &d, ambiguous == "reject" ? ROGTK_BC_REJECT : ROGTK_BC_COUNTS, nullptr,
+                                     index.data(), status.data(), nullptr, nullptr, nullptr, totals));
+    std::vector<uint8_t> valid((size_t)std::max<int64_t>((f.n + 63) / 64, 1) * 8, 0);
+    int64_t nulls = 0;
+    for (int64_t i = 0; i < f.n; ++i) {
+        if (status[(size_t)i] <= ROGTK_BC_CORRECTED) valid[(size_t)(i >> 3)] |= (uint8_t)(1u << (i & 7));
+        else ++nulls;
+    }
+    index.resize((size_t)f.n);
+    std::vector<Col> chunks;
+    chunks.push_back(prim_col<uint32_t>(nulls ? valid : std::vector<uint8_t>{}, nulls, std::move(index), f.n));
+    export_series(out, {s.name, "I", {}}, std::move(chunks));
+}
+
 int64_t phred_base(const Kwargs& kw) {
     const int64_t b = kw.uint("base");  // Phred2NmKwargs.base: u8 (expressions.rs:493-496)
     if (b > 255) fail("could not parse kwargs: base does not fit in u8");
@@ -1337,5 +1376,10 @@ ROGTK_FIELD(fuzzy_replace_expr, (FieldSpec{name, "vu", {}}))
 // UMI correction: the representative UMI of every row's H3 cluster
 ROGTK_EXPR(umi_correct_expr, umi_correct_expr(inputs, n_inputs, parse_kwargs(kwargs_ptr, kwargs_len), return_value))
 ROGTK_FIELD(umi_correct_expr, (FieldSpec{name, "vu", {}}))
+
+// cell-barcode correction: the whitelist index of every row
+ROGTK_EXPR(barcode_correct_expr,
+           barcode_correct_expr(inputs, n_inputs, parse_kwargs(kwargs_ptr, kwargs_len), return_value))
+ROGTK_FIELD(barcode_correct_expr, (FieldSpec{name, "I", {}}))
 
 }  // extern "C"

@@ -484,4 +484,29 @@ int irregular_cluster_grouped(const void* offsets, int offset_width, const uint8
                               uint32_t id_base, uint32_t* cluster_id, uint32_t* cluster_group,
                               int64_t* n_irregular_clusters, hipStream_t s);
 
+// ------------------------------------- cell-barcode correction (barcode.hip)
+// how k_bc_probe spreads a miss's lookups, and (measurements only) whether a lookup goes
+// through the prefix table; rogtk_barcode_set_probe takes the sum
+enum { kBarcodeProbeWave = 0, kBarcodeProbeLane = 1, kBarcodePlainSearch = 2 };
+int barcode_set_probe(int probe);
+// host_codes[W]: the whitelist's 2-bit codes in the caller's order (validated by the caller but
+// for duplicates, which the sort finds: ROGTK_E_INVALID names the first repeating row).
+// Synchronises s; the handle is bound to the current device.
+int barcode_whitelist_build(const uint64_t* host_codes, int64_t W, int L, void** out, hipStream_t s);
+void barcode_whitelist_free(void* handle);
+int barcode_whitelist_info(const void* handle, int64_t* W, int* L, int* prefix_digits, int64_t* device_bytes);
+// a device string column against the whitelist. count_only: the exact pass alone, adding into
+// exact_counts (index / status / counts unused). Otherwise exact_counts and counts (both
+// nullable) are overwritten. totals5 on the host. Synchronises s.
+int barcode_correct(const void* handle, const void* offsets, int ow, const uint8_t* values, const uint8_t* validity,
+                    int64_t voff, int64_t n, int ambiguous, const uint32_t* prior_counts, uint32_t* index,
+                    uint8_t* status, uint32_t* exact_counts, uint32_t* counts, bool count_only, int64_t* totals5,
+                    hipStream_t s);
+// the corrected strings: out_offsets[n + 1] = scan of (status <= 1 ? L : 0), then the bytes
+int barcode_corrected_temp(int64_t n, int64_t* bytes);
+int barcode_corrected_measure(const void* handle, const uint8_t* status, int64_t n, int64_t* out_offsets, void* temp,
+                              int64_t temp_bytes, hipStream_t s);
+int barcode_corrected_fill(const void* handle, const uint32_t* index, const uint8_t* status, int64_t n,
+                           const int64_t* out_offsets, uint8_t* out_values, hipStream_t s);
+
 }  // namespace rogtk

@@ -42,6 +42,8 @@ EXPRESSIONS = (
     "fuzzy_contains_native_expr", "fuzzy_replace_native_expr", "fuzzy_contains_expr", "fuzzy_replace_expr",
     # UMI correction (no reference counterpart)
     "umi_correct_expr",
+    # cell-barcode correction against a whitelist (no reference counterpart)
+    "barcode_correct_expr",
 )
 
 
@@ -293,6 +295,17 @@ def register_polars():
             return reg("umi_correct_expr", args,
                        {"umi_len": umi_len, "max_distance": max_distance, "method": method}, is_elementwise=False)
 
+    @pl.api.register_expr_namespace("barcode")
+    class BarcodeNamespace:  # no reference counterpart
+        def __init__(self, expr):
+            self._expr = expr
+
+        def correct(self, whitelist, ambiguous: str = "counts"):
+            # whitelist: a string expression or series of any length; not elementwise (the
+            # prior counts are the whole column's). The output is the whitelist index (UInt32).
+            return reg("barcode_correct_expr", [self._expr, whitelist], {"ambiguous": ambiguous},
+                       is_elementwise=False)
+
     def umi_complexity_scores(expr):  # :493-526
         return reg("umi_complexity_all_expr", expr, is_elementwise=True)
 
@@ -336,7 +349,7 @@ def register_polars():
                     "explore_k": explore_k, "prioritize_length": prioritize_length},
                    returns_scalar=True, is_elementwise=False)
 
-    return {"HammingExpr": HammingExpr, "FuzzyExpr": FuzzyExpr, "UmiNamespace": UmiNamespace, "umi_complexity_scores": umi_complexity_scores,
+    return {"HammingExpr": HammingExpr, "FuzzyExpr": FuzzyExpr, "UmiNamespace": UmiNamespace, "BarcodeNamespace": BarcodeNamespace, "umi_complexity_scores": umi_complexity_scores,
             "assemble_sequences": assemble_sequences,
             "assemble_sequences_with_anchors": assemble_sequences_with_anchors,
             "sweep_assembly_params": sweep_assembly_params, "optimize_assembly": optimize_assembly}
