@@ -2417,14 +2417,17 @@ __global__ __launch_bounds__(kPartBlock) void k_part_bitmap(const uint32_t* __re
         out[k] = (uint64_t)lbits[2 * k] | ((uint64_t)lbits[2 * k + 1] << 32);
 }
 
-// ---- mark by code slices in LDS (umi_len 7..12, default)
+// ---- mark by code slices in LDS, row mode (umi_len 7..12 where the 16-bit path below
+// does not apply: n < 2^20, umi_len <= 8, ROGTK_SLICE_BUCKETS=0)
 // The code space is cut into slices of 2^20 codes (128 KB of LDS as a bitmap) and the
 // rows into kSliceChunks chunks; workgroup (slice s, chunk c) reads chunk c's codes and
 // sets the bits of the codes that fall in slice s, then stores its slice of chunk c's
 // partial bitmap; one pass ORs the chunks' partials. Every code is read once from HBM:
 // the slices of one chunk are the workgroups b = s * chunks + c, which share the XCD
 // c % 8 under the round-robin placement (measured exact; speed only), so their repeated
-// reads of the chunk hit that XCD's L2. No sort, no scattered global stores.
+// reads of the chunk hit that XCD's L2. No sort, no scattered global stores. (Rounds 3-6
+// ran a segment mode in front of it, 32-bit entries per (slice, bucket workgroup) with a
+// cap and a fall-back to the rows; the 16-bit path below replaced it: DESIGN §13.)
 #ifndef ROGTK_SLICE_BLOCK
 #define ROGTK_SLICE_BLOCK 1024
 #endif
@@ -2434,77 +2437,18 @@ constexpr int kSliceChunks = 8;    // a multiple of the 8 XCDs (round 3: 8 vs 16
 #define ROGTK_SLICE_LOG2 20
 #endif
 constexpr int kSliceLog2 = ROGTK_SLICE_LOG2;  // codes per slice (LDS bits)
-constexpr int kSliceBits = 24 - kSliceLog2;   // log2 of the slices of 4^12
-constexpr int kMaxSlices = 1 << kSliceBits;
-constexpr int kBucketRows = 8192;  // rows per segment workgroup (8 per lane; default)
-constexpr int kSegCap = kBucketRows * 4 / kMaxSlices;  // codes per (slice, workgroup) segment: 4x the mean share
 
-// Segment mode (segs != nullptr, written by k_slice_bucket): workgroup (s, c) reads only
-// slice s's segments of the bucket workgroups of chunk c (every code is read once in
-// all); if one of them overflowed, it reads those workgroups' rows instead.
 __global__ __launch_bounds__(kSliceBlock) void k_slice_mark(const uint32_t* __restrict__ codes,
                                                             const uint64_t* __restrict__ regbits, int64_t n,
                                                             int slice_log2, int chunks, int64_t chunk_rows,
-                                                            uint64_t* __restrict__ out, int64_t words,
-                                                            const uint32_t* __restrict__ segs = nullptr,
-                                                            const uint32_t* __restrict__ seglen = nullptr,
-                                                            int nbuckets = 0, int bucket_rows = kBucketRows,
-                                                            int seg_cap = kSegCap) {
+                                                            uint64_t* __restrict__ out, int64_t words) {
     __shared__ uint32_t sbits[(1u << kSliceLog2) / 32];  // 128 KB at 2^20: the slice's bits (2^slice_log2 used)
     const int c = blockIdx.x % chunks, sl = blockIdx.x / chunks;
     const uint32_t sw32 = (1u << slice_log2) >> 5;
     for (uint32_t k = threadIdx.x; k < sw32; k += kSliceBlock) sbits[k] = 0;
     __syncthreads();
     const uint32_t smask = (1u << slice_log2) - 1u;
-    int64_t r0 = (int64_t)c * chunk_rows, r1 = min(n, r0 + chunk_rows);
-    if (segs) {
-        // the bucket workgroups of this chunk; a segment longer than kSegCap was not stored
-        // (its workgroup overflowed): then this chunk's rows are read instead
-        const int b0 = (int)((int64_t)c * nbuckets / chunks), b1 = (int)((int64_t)(c + 1) * nbuckets / chunks);
-        bool over = false;
-        for (int b = b0 + (int)threadIdx.x; b < b1; b += kSliceBlock)
-            over |= seglen[(int64_t)sl * nbuckets + b] > (uint32_t)seg_cap;
-        r0 = (int64_t)b0 * bucket_rows;
-        r1 = min(n, (int64_t)b1 * bucket_rows);
-        if (!__syncthreads_or(over)) {
-            // a wave takes kSegInFlight segments at a time (256 codes of each per pass of 16-B
-            // loads), all their loads in flight before the LDS atomics: one segment at a time
-            // left a wave ~2 dependent HBM round trips per segment (~10 segments per wave at
-            // 10M rows, ~60 at 62.5M: the C4 rank's 736 us, round 6)
-            constexpr int kSegInFlight = 8;
-            constexpr int kWaves = kSliceBlock / 64;
-            const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-            for (int bb = b0 + wave; bb < b1; bb += kWaves * kSegInFlight) {
-                uint32_t len[kSegInFlight];
-                uint32_t mx = 0;
-#pragma unroll
-                for (int u = 0; u < kSegInFlight; ++u) {
-                    const int b = bb + u * kWaves;
-                    len[u] = b < b1 ? seglen[(int64_t)sl * nbuckets + b] : 0u;
-                    mx = max(mx, len[u]);
-                }
-                for (uint32_t i = 4 * lane; i < mx; i += 256) {
-                    uint4 v[kSegInFlight];
-#pragma unroll
-                    for (int u = 0; u < kSegInFlight; ++u) {
-                        const uint32_t* seg = segs + ((int64_t)sl * nbuckets + bb + u * kWaves) * seg_cap;
-                        v[u] = i < len[u] ? *reinterpret_cast<const uint4*>(seg + i) : make_uint4(0, 0, 0, 0);
-                    }
-#pragma unroll
-                    for (int u = 0; u < kSegInFlight; ++u) {
-                        const uint32_t cc[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-#pragma unroll
-                        for (int k = 0; k < 4; ++k)
-                            if (i + k < len[u]) {
-                                const uint32_t b2 = cc[k] & smask;
-                                atomicOr(&sbits[b2 >> 5], 1u << (b2 & 31));
-                            }
-                    }
-                }
-            }
-            r1 = r0;  // no row pass
-        }
-    }
+    const int64_t r0 = (int64_t)c * chunk_rows, r1 = min(n, r0 + chunk_rows);
     // kSliceUnroll independent 16-B loads in flight per lane before the LDS atomics that
     // consume them (one load per iteration left the kernel latency-bound: 125 us)
     constexpr int kSliceUnroll = 8;
@@ -2545,34 +2489,63 @@ __global__ __launch_bounds__(kSliceBlock) void k_slice_mark(const uint32_t* __re
         o[k] = (uint64_t)sbits[2 * k] | ((uint64_t)sbits[2 * k + 1] << 32);
 }
 
-// Pass 1 of the segment mode: one workgroup per kBucketRows rows ranks its valid codes
-// by slice (lanes of a wave with one slice found by 4 ballots, one LDS atomic per slice
-// and wave) and stores them into its own segment of each slice (kSegCap codes, 4x the
-// mean share at 16 slices), with the segment lengths: no global atomics (a global
-// cursor per slice, hit by every workgroup, serialised the pass to 236 us). A segment
-// that would overflow is not stored (its length says so), and the slice pass reads the
-// rows of that chunk instead.
-constexpr int kBucketThreads = 1024;  // 8 rows per lane: short rank chains per wave
-template <int kBucketRows, int kBucketThreads>
-__global__ __launch_bounds__(kBucketThreads) void k_slice_bucket(const uint32_t* __restrict__ codes,
-                                                         const uint64_t* __restrict__ regbits, int64_t n,
-                                                         int slice_log2, int nslices, uint32_t* __restrict__ segs,
-                                                         uint32_t* __restrict__ seglen, int nbuckets) {
-    __shared__ unsigned int cnt[kMaxSlices], lbase[kMaxSlices + 1];
-    constexpr int kSegCap = kBucketRows * 4 / kMaxSlices;  // 4x the mean share
-    __shared__ uint32_t stage[kBucketRows];
+__global__ __launch_bounds__(kBlock) void k_or_partials(const uint64_t* __restrict__ partials, int chunks,
+                                                        int64_t words, uint64_t* __restrict__ out) {
+    for (int64_t w = (int64_t)blockIdx.x * kBlock + threadIdx.x; w < words; w += (int64_t)gridDim.x * kBlock) {
+        uint64_t v = 0;
+        for (int c = 0; c < chunks; ++c) v |= __builtin_nontemporal_load(partials + (int64_t)c * words + w);
+        out[w] = v;
+    }
+}
+
+// ---- mark by 2^16-code slices with 16-bit entries (umi_len 9..12 at n >= 2^20, default)
+// Two passes, no chunk partials. The bucket pass (k_slice_bucket16) sorts each
+// kB16Rows consecutive rows by slice code >> 16 in LDS and stores them as one dense
+// block of uint16 entries (code & 0xFFFF: the slice implies the rest), every slice's run
+// padded to 8 entries so it starts 16-B aligned, with a table of (start, length) per
+// (slice, bucket). There is no per-run cap, so nothing overflows and nothing falls back
+// to the rows: a bucket whose rows share one slice is one run of kB16Rows entries. The
+// slice pass (k_slice_mark16) is one workgroup per slice: it holds the slice's 2^16 bits
+// in 8 KB of LDS, reads its run of every bucket and stores its 1024 words of the final
+// bitmap itself. 256 slices at umi_len 12 are one workgroup per CU, so the row chunks,
+// their partial bitmaps and the OR pass of the 2^20-code slices are not needed.
+#ifndef ROGTK_B16_ROWS
+#define ROGTK_B16_ROWS 8192
+#endif
+#ifndef ROGTK_S16_BLOCK
+#define ROGTK_S16_BLOCK 512
+#endif
+constexpr int kS16Log2 = 16;                              // codes per slice: the entry is a uint16
+constexpr int kS16MaxSlices = 1 << (24 - kS16Log2);       // 256 at umi_len 12
+constexpr int kB16Rows = ROGTK_B16_ROWS;                  // rows per bucket workgroup (8 per lane; 16384: 0.2711-0.2764 vs 0.2721-0.2777 ms/step, no gain, round 7)
+constexpr int kB16Threads = 1024;
+constexpr int kB16Stride = kB16Rows + 8 * kS16MaxSlices;  // entries of a bucket's block (runs padded to 8: <= rows + 7 * slices)
+constexpr int kS16Block = ROGTK_S16_BLOCK;  // beside the score kernel: 512 threads 21-23 us, 256 26 us, 1024 31-32 us (round 7)
+constexpr int kS16InFlight = 8;  // runs a lane group holds in flight per trip
+static_assert(kB16Stride < 65536 && kB16Rows % (4 * kB16Threads) == 0, "(start, length) are uint16 pairs");
+
+// Bucket pass: a returning LDS add on cnt[slice] ranks a row within its slice (random
+// codes over 256 counters rarely meet in one wave instruction), one wave scans the padded
+// counts, the codes are staged sorted in LDS and the block leaves in 16-B stores.
+template <int kRows, int kThreads>
+__global__ __launch_bounds__(kThreads) void k_slice_bucket16(const uint32_t* __restrict__ codes,
+                                                             const uint64_t* __restrict__ regbits, int64_t n,
+                                                             int nslices, uint16_t* __restrict__ blocks,
+                                                             uint32_t* __restrict__ table, int nbuckets) {
+    __shared__ unsigned int cnt[kS16MaxSlices], start[kS16MaxSlices], total;
+    __shared__ __attribute__((aligned(16))) uint16_t stage[kRows + 8 * kS16MaxSlices];
     const int t = threadIdx.x, lane = t & 63;
-    if (t < kMaxSlices) cnt[t] = 0;
+    if (t < kS16MaxSlices) cnt[t] = 0;
     __syncthreads();
-    const int64_t row0 = (int64_t)blockIdx.x * kBucketRows;
-    constexpr int kPer = kBucketRows / kBucketThreads / 4;  // uint4 loads per lane
-    uint32_t key[kPer * 4];  // slice << 16 | index within the slice's segment, or kNone
+    const int64_t row0 = (int64_t)blockIdx.x * kRows;
+    constexpr int kPer = kRows / kThreads / 4;  // uint4 loads per lane
+    uint32_t key[kPer * 4];  // slice << 16 | rank within the slice's run, or kNone
     uint32_t val[kPer * 4];
     uint32_t regs[kPer];
     // all kPer 16-B loads in flight before the ranking that consumes them
 #pragma unroll
     for (int u = 0; u < kPer; ++u) {
-        const int64_t r = row0 + 4 * ((int64_t)u * kBucketThreads + t);
+        const int64_t r = row0 + 4 * ((int64_t)u * kThreads + t);
         uint4 v = make_uint4(0, 0, 0, 0);
         uint32_t reg = 0;
         if (r + 4 <= n) {
@@ -2594,69 +2567,108 @@ __global__ __launch_bounds__(kBucketThreads) void k_slice_bucket(const uint32_t*
     for (int u = 0; u < kPer; ++u) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const uint32_t sl = val[4 * u + k] >> slice_log2;
-            const bool ok = ((regs[u] >> k) & 1u) && sl < (uint32_t)nslices;
-            uint64_t peers = __ballot(ok);
+            const uint32_t sl = val[4 * u + k] >> kS16Log2;
+            const bool ok = ((regs[u] >> k) & 1u) && sl < (uint32_t)nslices;  // codes >= 4^L: no slice
+            key[4 * u + k] = ok ? (sl << 16) | atomicAdd(&cnt[sl], 1u) : kNone;
+        }
+    }
+    __syncthreads();
+    if (t < 64) {  // exclusive scan of the 256 padded counts, 4 per lane
+        unsigned int pre[4], sum = 0;
 #pragma unroll
-            for (int bit = 0; bit < kSliceBits; ++bit) {
-                const uint64_t b = __ballot((sl >> bit) & 1u);
-                peers &= ((sl >> bit) & 1u) ? b : ~b;
-            }
-            const int leader = peers ? __ffsll((long long)peers) - 1 : 0;
-            unsigned int base = 0;
-            if (ok && lane == leader) base = atomicAdd(&cnt[sl], (unsigned int)__popcll(peers));
-            base = __shfl(base, leader);
-            key[4 * u + k] = ok ? (sl << 16) | (base + (uint32_t)__popcll(peers & ((1ull << lane) - 1ull))) : kNone;
+        for (int j = 0; j < 4; ++j) {
+            pre[j] = sum;
+            sum += (cnt[4 * t + j] + 7u) & ~7u;
         }
+        unsigned int inc = sum;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned int o = __shfl_up(inc, d);
+            if (lane >= d) inc += o;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) start[4 * t + j] = inc - sum + pre[j];
+        if (t == 63) total = inc;
     }
     __syncthreads();
-    if (t < nslices) seglen[(int64_t)t * nbuckets + blockIdx.x] = cnt[t];  // > kSegCap: not stored
-    if (t == 0) {
-        unsigned int acc = 0;
-        for (int k = 0; k < nslices; ++k) {
-            lbase[k] = acc;
-            acc += cnt[k];
-        }
-        lbase[nslices] = acc;
-    }
-    __syncthreads();
-    // stage sorted by slice in LDS, then store each slice's run contiguously
+    if (t < nslices) table[(int64_t)t * nbuckets + blockIdx.x] = start[t] | (cnt[t] << 16);
 #pragma unroll
     for (int u = 0; u < kPer * 4; ++u) {
         const uint32_t kk = key[u];
-        if (kk != kNone) stage[lbase[kk >> 16] + (kk & 0xFFFFu)] = val[u];
+        if (kk != kNone) stage[start[kk >> 16] + (kk & 0xFFFFu)] = (uint16_t)val[u];
     }
     __syncthreads();
-    const unsigned int total = lbase[nslices];
-    for (unsigned int i = t; i < total; i += kBucketThreads) {
-        const uint32_t c = stage[i];
-        const uint32_t sl = c >> slice_log2;
-        if (cnt[sl] <= (unsigned int)kSegCap) segs[((int64_t)sl * nbuckets + blockIdx.x) * kSegCap + (i - lbase[sl])] = c;
-    }
+    // the pad entries of a run carry whatever the stage held: the table's length masks them
+    const uint4* s4 = reinterpret_cast<const uint4*>(stage);
+    uint4* o4 = reinterpret_cast<uint4*>(blocks + (int64_t)blockIdx.x * kB16Stride);
+    for (unsigned int i = t; i < total / 8; i += kThreads) o4[i] = s4[i];
 }
 
-__global__ __launch_bounds__(kBlock) void k_or_partials(const uint64_t* __restrict__ partials, int chunks,
-                                                        int64_t words, uint64_t* __restrict__ out) {
-    for (int64_t w = (int64_t)blockIdx.x * kBlock + threadIdx.x; w < words; w += (int64_t)gridDim.x * kBlock) {
-        uint64_t v = 0;
-        for (int c = 0; c < chunks; ++c) v |= __builtin_nontemporal_load(partials + (int64_t)c * words + w);
-        out[w] = v;
+// Slice pass: workgroup sl ORs slice sl's run of every bucket into its LDS bits. A group
+// of kG lanes takes kS16InFlight buckets per trip (one 16-B load = 8 entries per lane and
+// run, all of a trip's loads issued before the first LDS atomic; the next trip's table
+// entries are loaded before this trip's runs): kG * 8 entries cover the mean run in one
+// pass (32 entries at 256 slices and 8192-row buckets, 128 at 64 slices).
+template <int kThreads, int kG>
+__global__ __launch_bounds__(kThreads) void k_slice_mark16(const uint16_t* __restrict__ blocks,
+                                                           const uint32_t* __restrict__ table, int nbuckets,
+                                                           uint64_t* __restrict__ bitmap) {
+    __shared__ uint32_t sbits[(1u << kS16Log2) / 32];
+    constexpr int kWords32 = (1 << kS16Log2) / 32;
+    constexpr int kGroups = kThreads / kG, kU = kS16InFlight;
+    const int t = threadIdx.x, g = t / kG, gl = t % kG, sl = blockIdx.x;
+    for (int k = t; k < kWords32; k += kThreads) sbits[k] = 0;
+    __syncthreads();
+    const uint32_t* tab = table + (int64_t)sl * nbuckets;
+    uint32_t te[kU];  // start | length << 16 of this trip's runs
+#pragma unroll
+    for (int u = 0; u < kU; ++u) te[u] = g + u * kGroups < nbuckets ? tab[g + u * kGroups] : 0u;
+    for (int bb = g; bb < nbuckets; bb += kGroups * kU) {
+        uint32_t nx[kU], mx = 0;
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const int b = bb + (kU + u) * kGroups;
+            nx[u] = b < nbuckets ? tab[b] : 0u;
+            mx = max(mx, te[u] >> 16);
+        }
+        for (uint32_t i = 8 * gl; i < mx; i += 8 * kG) {
+            uint4 v[kU];
+#pragma unroll
+            for (int u = 0; u < kU; ++u) {
+                const uint16_t* run = blocks + (int64_t)(bb + u * kGroups) * kB16Stride + (te[u] & 0xFFFFu);
+                v[u] = i < (te[u] >> 16) ? *reinterpret_cast<const uint4*>(run + i) : make_uint4(0, 0, 0, 0);
+            }
+#pragma unroll
+            for (int u = 0; u < kU; ++u) {
+                const uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+                const uint32_t len = te[u] >> 16;
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    if (i + k < len) {
+                        const uint32_t c = (w[k >> 1] >> (16 * (k & 1))) & 0xFFFFu;
+                        atomicOr(&sbits[c >> 5], 1u << (c & 31));
+                    }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kU; ++u) te[u] = nx[u];
     }
+    __syncthreads();
+    uint64_t* o = bitmap + (int64_t)sl * (kWords32 / 2);
+    for (int k = t; k < kWords32 / 2; k += kThreads) o[k] = (uint64_t)sbits[2 * k] | ((uint64_t)sbits[2 * k + 1] << 32);
 }
 
-// chunks of the slice mark for n rows (1 = the slices write the bitmap directly; with one
-// chunk at 10M rows only 16 workgroups run: measured 2x slower; 16 chunks measured slower
-// than 8, round 3)
+inline int64_t b16_buckets(int64_t n) { return (n + kB16Rows - 1) / kB16Rows; }
+inline int64_t b16_block_bytes(int64_t n) { return b16_buckets(n) * kB16Stride * 2; }  // a multiple of 16
+inline int64_t b16_bytes(int64_t n) { return b16_block_bytes(n) + (int64_t)kS16MaxSlices * b16_buckets(n) * 4; }
+// the 16-bit path takes (n, L): more than one 2^16 slice and enough rows for the bucket pass
+inline bool slice16_applies(int64_t n, int L) { return L >= 9 && L <= 12 && n >= (1 << 20); }
+
+// chunks of the row-mode slice mark for n rows (1 = the slices write the bitmap directly;
+// with one chunk at 10M rows only 16 workgroups run: measured 2x slower; 16 chunks measured
+// slower than 8, round 3)
 inline int slice_chunks(int64_t n) { return n >= (1 << 20) ? kSliceChunks : 1; }
-inline bool slice_segments(int64_t n) { return n >= (1 << 20); }  // the bucket pass runs
-inline int slices_of(int L) { return 1 << (2 * L - std::min(2 * L, kSliceLog2)); }
-inline int64_t seg_buckets(int64_t n) { return (n + kBucketRows - 1) / kBucketRows; }
-// segments + their lengths of the segment mode (bucket workgroups of 2048 / 4096 rows
-// measured neutral against 8192, round 3)
-inline int64_t seg_bytes(int64_t n) {
-    return ((int64_t)kMaxSlices * seg_buckets(n) * kSegCap * 4) + ((int64_t)kMaxSlices * seg_buckets(n) * 4 + 255) / 256 * 256;
-}
-// ROGTK_SLICE_BUCKETS=0: slices read all rows (A/B)
+// ROGTK_SLICE_BUCKETS=0: no bucket pass, the 2^20-code slices read all rows (A/B)
 inline bool slice_buckets_on() {
     static const bool on = [] {
         const char* e = getenv("ROGTK_SLICE_BUCKETS");
@@ -2695,11 +2707,9 @@ int cluster_mark_bitmap_temp(int64_t n, int L, int64_t* bytes) {
     // both methods' scratch, so that the method can be switched on a live buffer
     const int64_t sort_bytes = 2 * ((nn * 4 + 255) / 256 * 256) + (int64_t)part_sort_temp(nn) + 256;
     const int64_t words = ((int64_t)1 << (2 * L)) / 64;
-    int64_t slice_bytes = 0;
-    if (L <= 12 && slice_segments(nn)) {
-        slice_bytes = slice_chunks(nn) > 1 ? (int64_t)slice_chunks(nn) * words * 8 : 0;
-        if (slices_of(L) > 1) slice_bytes += seg_bytes(nn);
-    }
+    // the chunk partials of the row mode, or the blocks + table of the 16-bit path
+    int64_t slice_bytes = L <= 12 && slice_chunks(nn) > 1 ? (int64_t)slice_chunks(nn) * words * 8 : 0;
+    if (slice16_applies(nn, L)) slice_bytes = std::max(slice_bytes, b16_bytes(nn));
     *bytes = std::max(sort_bytes, slice_bytes);
     return ROGTK_OK;
 }
@@ -2709,9 +2719,9 @@ int launch_cluster_mark_bitmap(const uint32_t* codes, const uint64_t* regular_bi
     return launch_cluster_mark_phase(codes, regular_bits, n, L, bitmap, temp, temp_bytes, 0, s);
 }
 
-// phase 0: the whole mark; 1: the slice-bucket pass alone (nothing when the code-slice
-// segments do not apply to (n, L)); 2: the rest (slice mark + OR of the chunk partials, or
-// the partition sort), to be enqueued after phase 1 (round 5: the pipeline runs phase 1 on
+// phase 0: the whole mark; 1: the slice-bucket pass alone (nothing when the 16-bit path
+// does not apply to (n, L)); 2: the rest (the slice pass; or the row-mode slice mark + OR of
+// the chunk partials; or the partition sort), to be enqueued after phase 1 (round 5: the pipeline runs phase 1 on
 // the main stream and phase 2 at the head of the resolve stream, beside the score kernel)
 int launch_cluster_mark_phase(const uint32_t* codes, const uint64_t* regular_bits, int64_t n, int L,
                               uint64_t* bitmap, void* temp, int64_t temp_bytes, int phase, hipStream_t s) {
@@ -2727,6 +2737,30 @@ int launch_cluster_mark_phase(const uint32_t* codes, const uint64_t* regular_bit
         return ROGTK_OK;
     }
     ROGTK_REQUIRE(((uintptr_t)codes & 15u) == 0, ROGTK_E_INVALID, "mark_bitmap: codes must be 16-byte aligned");
+    if (use_slices(L) && slice16_applies(n, L) && slice_buckets_on()) {
+        // 2^16-code slices, 16-bit entries: the bucket pass, then one workgroup per slice
+        const int slices = 1 << (two_l - kS16Log2);
+        const int nb = (int)b16_buckets(n);
+        uint16_t* blocks = (uint16_t*)temp;
+        uint32_t* table = (uint32_t*)((uint8_t*)temp + b16_block_bytes(n));
+        if (phase != 2)
+            ROGTK_TIMED_LAUNCH(K_K_SLICE_BUCKET, (k_slice_bucket16<kB16Rows, kB16Threads>), dim3((unsigned)nb),
+                               dim3(kB16Threads), 0, s, codes, regular_bits, n, slices, blocks, table, nb);
+        if (phase != 1) {
+            // lanes per run: 8 entries per lane cover the mean run (kB16Rows / slices) in one pass
+            if (slices >= 256)
+                ROGTK_TIMED_LAUNCH(K_K_SLICE_MARK, (k_slice_mark16<kS16Block, 8>), dim3((unsigned)slices), dim3(kS16Block),
+                                   0, s, (const uint16_t*)blocks, (const uint32_t*)table, nb, bitmap);
+            else if (slices >= 64)
+                ROGTK_TIMED_LAUNCH(K_K_SLICE_MARK, (k_slice_mark16<kS16Block, 32>), dim3((unsigned)slices), dim3(kS16Block),
+                                   0, s, (const uint16_t*)blocks, (const uint32_t*)table, nb, bitmap);
+            else
+                ROGTK_TIMED_LAUNCH(K_K_SLICE_MARK, (k_slice_mark16<kS16Block, 64>), dim3((unsigned)slices), dim3(kS16Block),
+                                   0, s, (const uint16_t*)blocks, (const uint32_t*)table, nb, bitmap);
+        }
+        ROGTK_HIP_CHECK(hipGetLastError());
+        return ROGTK_OK;
+    }
     if (use_slices(L)) {
         const int slog = std::min(two_l, kSliceLog2);
         const int slices = 1 << (two_l - slog);
@@ -2735,25 +2769,9 @@ int launch_cluster_mark_phase(const uint32_t* codes, const uint64_t* regular_bit
         chunk_rows = (chunk_rows + 3) / 4 * 4;  // rows of a chunk start 4-aligned (uint4 loads)
         const int64_t words = ((int64_t)1 << two_l) / 64;
         uint64_t* dst = chunks > 1 ? (uint64_t*)temp : bitmap;
-        const uint32_t* segs = nullptr;
-        uint32_t* seglen = nullptr;
-        const int nb = (int)seg_buckets(n);
-        if (slice_segments(n) && slices > 1 && slices <= kMaxSlices && slice_buckets_on()) {
-            // segment pass: every slice workgroup then reads only its slice's codes (the
-            // chunks of all rows were read once per slice: 16x at L = 12, from L2)
-            segs = (const uint32_t*)((uint8_t*)temp + (chunks > 1 ? (int64_t)chunks * words * 8 : 0));
-            seglen = (uint32_t*)((uint8_t*)segs + (int64_t)kMaxSlices * nb * kSegCap * 4);
-            if (phase != 2)
-                ROGTK_TIMED_LAUNCH(K_K_SLICE_BUCKET, (k_slice_bucket<kBucketRows, kBucketThreads>), dim3((unsigned)nb),
-                                   dim3(kBucketThreads), 0, s, codes, regular_bits, n, slog, slices, (uint32_t*)segs,
-                                   seglen, nb);
-        }
-        if (phase == 1) {
-            ROGTK_HIP_CHECK(hipGetLastError());
-            return ROGTK_OK;
-        }
+        if (phase == 1) return ROGTK_OK;  // the row mode has no bucket pass
         ROGTK_TIMED_LAUNCH(K_K_SLICE_MARK, k_slice_mark, dim3((unsigned)(slices * chunks)), dim3(kSliceBlock), 0, s, codes, regular_bits,
-                           n, slog, chunks, chunk_rows, dst, words, segs, (const uint32_t*)seglen, nb, kBucketRows, kSegCap);
+                           n, slog, chunks, chunk_rows, dst, words);
         if (chunks > 1)
             ROGTK_TIMED_LAUNCH(K_K_OR_PARTIALS, k_or_partials, dim3(grid_for(words, 4096)), dim3(kBlock), 0, s, dst, chunks, words,
                                bitmap);
