@@ -1550,8 +1550,10 @@ __global__ __launch_bounds__(kBlock) void k_word_label(const uint32_t* __restric
                 }
             }
         }
-        // bit 31 flags a word with exceptions (mask form: labels < 2^29, umi_len <= 14; a
-        // larger label leaves the word unlabelled and all its codes are labelled per code)
+        // bit 31 flags a word with exceptions (mask form: labels < 2^29, which holds every
+        // label for umi_len <= 15: clusters are pairwise non-adjacent, so there are at most
+        // 4^(L-1) <= 4^14 < 2^29 of them; a larger label, umi_len 16 with > 5e8 clusters,
+        // leaves the word unlabelled and all its codes are labelled per code)
         uint32_t lab = root != kNone ? root_label(root, rbits, rpref, rblkoff) : kNone;
         if (exc && lab != kNone) {  // encodings: decode_word_label (rogtk_internal.h)
             const uint64_t rest = exc & (exc - 1);  // the exceptions past the first
