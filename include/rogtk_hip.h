@@ -416,6 +416,15 @@ int rogtk_kmer_lds_rows(int64_t* out);
  * examined, 1 = emptied (no k-mer can be valid), 2 = kept, 3 = kept (too many minimizers
  * to decide); other bytes are left as they were. Calls with more groups write nothing. */
 int rogtk_kmer_debug_filter(uint8_t* decisions, int64_t n_groups);
+/* Tests only: host_buf (HOST memory, 2 * n_groups bytes; NULL / 0 turns it off) receives the
+ * LDS size class of every group of the next calls with G <= n_groups groups (indices of the
+ * call): host_buf[g] = the class k_group_classify (and the minimizer filter) gave group g,
+ * host_buf[G + g] = its class after the last LDS kernel (0 = the global path, 5 = certified
+ * empty). Only the groups of the effective k a pass runs are written (a host call with
+ * several effective k fills the buffer pass by pass); a pass without the LDS path
+ * (rogtk_kmer_set_path(0), effective k 64) writes nothing. While a buffer is registered each
+ * pass costs two more copies and stream synchronisations; with none, nothing changes. */
+int rogtk_kmer_debug_classes(uint8_t* host_buf, int64_t n_groups);
 int rogtk_kmer_spectrum_host(const void* offsets, int offset_width, const uint8_t* values,
                              int64_t values_len, const uint8_t* validity, int64_t validity_offset,
                              int64_t n_rows, const int64_t* group_offsets, int64_t n_groups, int k,

@@ -2094,7 +2094,6 @@ __global__ __launch_bounds__(kBlock) void k_group_classify(const int64_t* __rest
         } else if (K <= 32 && obs > 0) {
             if (wave && K <= 16 && nrows <= kWaveRows && words <= kWaveWords) cls = 2;
             else if (wave && K <= 16 && nrows <= kWaveRows && words <= kWaveBigWords) cls = kClsWaveBig;
-            else if (wave && K <= 16 && nrows <= kWaveRows && words <= kWaveBigWords) cls = kClsWaveBig;
             else if (nrows <= LdsCfg<3>::kRows && words <= LdsCfg<3>::kWords) cls = 3;
             else if (nrows <= LdsCfg<1>::kRows && words <= LdsCfg<1>::kWords) cls = 1;
             else if (nrows <= LdsCfg<4>::kRows && words <= LdsCfg<4>::kWords) cls = 4;
@@ -2110,6 +2109,10 @@ std::atomic<int> g_kmer_mz{-1};
 // tests only (rogtk_kmer_debug_filter): per group of a call, the filter's decision
 uint8_t* g_mz_debug = nullptr;
 int64_t g_mz_debug_groups = 0;
+// tests only (rogtk_kmer_debug_classes): per group of a call, its class before and after
+// the LDS kernels, into a host buffer of 2 * g_cls_debug_groups bytes
+uint8_t* g_cls_debug = nullptr;
+int64_t g_cls_debug_groups = 0;
 inline bool kmer_mz_on() {
     int v = g_kmer_mz.load(std::memory_order_relaxed);
     if (v < 0) {
@@ -2732,6 +2735,17 @@ struct KIn {
     int64_t vlen = 0;                  // fused: readable bytes of values
 };
 
+// tests only: gsmall[0..G) of the groups of effective k K to dst (host), after the work queued on s
+int debug_classes_copy(KmerCtx* c, int64_t G, int K, const std::vector<uint8_t>* gk_host, uint8_t* dst,
+                       hipStream_t s) {
+    std::vector<uint8_t> cls((size_t)G);
+    ROGTK_HIP_CHECK(hipMemcpyAsync(cls.data(), c->gsmall.p, (size_t)G, hipMemcpyDeviceToHost, s));
+    ROGTK_HIP_CHECK(hipStreamSynchronize(s));
+    for (int64_t g = 0; g < G; ++g)
+        if (!gk_host || (*gk_host)[g] == K) dst[g] = cls[g];
+    return ROGTK_OK;
+}
+
 template <int OW, bool WIDE>
 int run_class(KmerCtx* c, const KIn& in, int64_t n_rows, int64_t G, int K, int64_t min_cov, hipStream_t s,
               const std::vector<uint8_t>* gk_host) {
@@ -2824,6 +2838,9 @@ int run_class(KmerCtx* c, const KIn& in, int64_t n_rows, int64_t G, int K, int64
                               c->packed.as<uint64_t>(), gstat, g_mz_debug_groups >= G ? g_mz_debug : nullptr);
         ROGTK_HIP_CHECK(hipGetLastError());
     }
+    const bool cls_debug = lds && g_cls_debug && g_cls_debug_groups >= G;  // tests only
+    if (cls_debug)
+        if (int rc = debug_classes_copy(c, G, K, gk_host, g_cls_debug, s)) return rc;
     if (lds && c->wave_path && K <= 16) {
         // classes 2 and 6 first: their overflowing groups become class 3 for the launch below
         const int64_t chunks = (G + 63) / 64;
@@ -2860,6 +2877,8 @@ int run_class(KmerCtx* c, const KIn& in, int64_t n_rows, int64_t G, int K, int64
                            c->woff.as<int64_t>(), stride, c->packed.as<uint64_t>(), in.cap_off, c->t_kmer.as<uint64_t>(),
                            c->t_ext.as<uint8_t>(), c->t_cnt.as<uint16_t>(), in.gcount, gstat, c->lo_only ? 1 : 0);
     }
+    if (cls_debug)
+        if (int rc = debug_classes_copy(c, G, K, gk_host, g_cls_debug + G, s)) return rc;
     // the groups per path first: with none on the global path (the usual C3 call, every
     // group in LDS or certified empty) its row drop and observation scan are skipped
     if (int rc = c->scal.ensure(64)) return rc;
@@ -3038,6 +3057,13 @@ int rogtk_kmer_debug_filter(uint8_t* decisions, int64_t n_groups) {
     ROGTK_REQUIRE(!decisions == !n_groups && n_groups >= 0, ROGTK_E_INVALID, "kmer_debug_filter: buffer and size");
     g_mz_debug = decisions;
     g_mz_debug_groups = n_groups;
+    return ROGTK_OK;
+}
+
+int rogtk_kmer_debug_classes(uint8_t* host_buf, int64_t n_groups) {
+    ROGTK_REQUIRE(!host_buf == !n_groups && n_groups >= 0, ROGTK_E_INVALID, "kmer_debug_classes: buffer and size");
+    g_cls_debug = host_buf;
+    g_cls_debug_groups = n_groups;
     return ROGTK_OK;
 }
 

@@ -140,6 +140,10 @@ def test_c3_path_1m_vs_oracle(k, min_cov, batch_rows, packed, filt, path):
         _lib.call("rogtk_kmer_set_path", 1)
     ps = (ctypes.c_int64 * 2)()
     _lib.call("rogtk_kmer_path_stats", ps)
+    # the stats are the last spectrum call's: every group of it on one of the two paths (all G
+    # groups when the run is one call), and under paths 1 and 2 some of them on the LDS path
+    assert ps[0] + ps[1] == calls[-1][1] - calls[-1][0] and (len(calls) > 1 or ps[0] + ps[1] == G), tuple(ps)
+    assert path not in (1, 2) or ps[0] > 0, tuple(ps)
     order = np.argsort(codes_h, kind="stable")
     assert np.array_equal(rows.cpu().numpy(), order)  # group_by: ids in code order, rows stable
     _, starts = np.unique(codes_h[order], return_index=True)
