@@ -533,10 +533,29 @@ typedef struct rogtk_str_col {
     int64_t n;
 } rogtk_str_col;
 
+/* The longest output row: what an int32-offset Arrow consumer can hold. A CIGAR number,
+ * not the input length, decides how long an aligned or parsed row gets ("4294967296I"
+ * is 11 bytes in, 4 GiB out), so the kernels bound every row by this cap: the
+ * measuring pass saturates at ROGTK_STR_MAX_ROW_BYTES + 1 in time proportional to the
+ * row's input bytes, and the filling pass writes nothing for such a row. */
+#define ROGTK_STR_MAX_ROW_BYTES 2147483647LL
+
 /* Level 1 (device columns, enqueue-only): measure writes out_offsets[n_rows + 1]
  * (exclusive scan of the output byte lengths; out_offsets[n_rows] = total) and the
- * output validity (bit per row, LSB order); the caller sizes out_values from the
- * total and calls fill. temp: rogtk_str_temp_bytes(n_rows) bytes of device memory. */
+ * output validity (bit per row, LSB order: one 64-bit word per 64 rows, bits at or
+ * above n_rows of the last word zero); the caller sizes out_values from the total and
+ * calls fill. temp: rogtk_str_temp_bytes(n_rows) bytes of device memory.
+ * Input columns: int32 or int64 offsets that need not start at 0 (values is the
+ * buffer the offsets index), validity read at bit validity_offset + row, a column of
+ * n == 1 beside n_rows > 1 broadcast (its row 0, null or not, for every row).
+ * Over the cap: a row whose output exceeds ROGTK_STR_MAX_ROW_BYTES stays valid and
+ * measures as exactly ROGTK_STR_MAX_ROW_BYTES + 1, meaning "over the cap, do not
+ * fill": the total then counts bytes that will never be written. Level 1 cannot
+ * report it (nothing is read back), so a caller that may see garbled CIGARs looks for
+ * out_offsets[i + 1] - out_offsets[i] > ROGTK_STR_MAX_ROW_BYTES before it allocates
+ * out_values; fill on such offsets skips those rows and writes the others at their
+ * offsets. n_rows < 2^31, so the scan cannot wrap. Level 2 returns
+ * ROGTK_E_UNSUPPORTED naming the first such row. */
 int rogtk_str_temp_bytes(int64_t n_rows, int64_t* bytes);
 int rogtk_str_measure(int op, const rogtk_str_col* cols, int n_cols, int64_t n_rows, int64_t param,
                       int64_t* out_offsets, uint64_t* out_valid_bits, void* temp, int64_t temp_bytes,

@@ -107,7 +107,11 @@ def extract_insertions(seq: str, cigar: str) -> Dict[int, str]:
             sp = (sp + n) & M64
             rp = (rp + n) & M64
         elif op == "I":
-            if (sp + n) & M64 <= len(sb):
+            # The reference tests the wrapped sum `seq_pos + len <= seq.len()` and then
+            # PANICS on the slice when the sum wrapped (seq_pos or len near 2^64). Here
+            # such a row is "insertion past the end of seq": no wrapping test, as the
+            # kernels (rogtk_amd/csrc/strings_rows.h).
+            if sp <= len(sb) and n <= len(sb) - sp:
                 ins[rp] = sb[sp:sp + n].decode("utf-8", "replace")  # String::from_utf8_lossy
             sp = (sp + n) & M64
         elif op in "DN":

@@ -11,12 +11,12 @@
 //   ROGTK_STR_PHRED_STR        phred_to_numeric_series_str / split_string :632-665
 //   ROGTK_STR_PHRED_LIST       phred_to_numeric_series (List[u8] values) :598-630
 //
-// Every op is ONE device function run twice over the rows (thread per row): a
-// measuring pass that only counts output bytes, then, after an exclusive scan of
-// the counts, a filling pass that writes them at the row's offset. The emitter is
-// the only difference between the passes, so the two can never disagree.
-// Arithmetic follows the reference's release build (Cargo.toml [profile.release]:
-// no overflow checks): usize sums wrap, `u8 - base` wraps.
+// Every op is ONE function (strings_rows.h, shared with a host harness) run twice
+// over the rows (thread per row): a measuring pass that only counts output bytes,
+// then, after an exclusive scan of the counts, a filling pass that writes them at the
+// row's offset. The emitter is the only difference between the passes, so the two can
+// never disagree. The per-row cap (ROGTK_STR_MAX_ROW_BYTES) and the insertion bounds
+// live in that header; this file holds the column layout, the kernels and the ABI.
 #include <hipcub/hipcub.hpp>
 
 #include <cstdlib>
@@ -24,9 +24,12 @@
 #include <vector>
 
 #include "rogtk_internal.h"
+#include "strings_rows.h"
 
 namespace rogtk {
 namespace {
+
+using namespace str_rows;
 
 constexpr int kBlock = 256;
 
@@ -53,354 +56,10 @@ __device__ __forceinline__ bool col_valid(const Col& c, int64_t i) {
     return (c.valid[b >> 3] >> (b & 7)) & 1;
 }
 
-struct Str {
-    const uint8_t* p;
-    uint64_t n;
-};
 __device__ __forceinline__ Str col_str(const Col& c, int64_t i) {
     if (c.bcast) i = 0;
     const int64_t a = col_off(c, i), b = col_off(c, i + 1);
     return Str{c.val + a, (uint64_t)(b - a)};
-}
-
-// Counting (FILL = false) or writing (FILL = true) output bytes.
-template <bool FILL>
-struct Emit {
-    uint8_t* p;
-    uint64_t n = 0;
-    __device__ __forceinline__ void put(uint8_t b) {
-        if (FILL) p[n] = b;
-        ++n;
-    }
-    __device__ __forceinline__ void fill(uint8_t b, uint64_t k) {
-        if (FILL)
-            for (uint64_t j = 0; j < k; ++j) p[n + j] = b;
-        n += k;
-    }
-    __device__ __forceinline__ void bytes(const uint8_t* s, uint64_t k) {
-        if (FILL)
-            for (uint64_t j = 0; j < k; ++j) p[n + j] = s[j];
-        n += k;
-    }
-    // `format!("{}", v)` of a usize / u8
-    __device__ __forceinline__ void dec(uint64_t v) {
-        uint8_t t[20];
-        int k = 0;
-        do {
-            t[k++] = (uint8_t)('0' + v % 10);
-            v /= 10;
-        } while (v);
-        while (k) put(t[--k]);
-    }
-    // `String::push((b as char).to_ascii_{upper,lower}case())`: a byte >= 0x80 is the
-    // Latin-1 char U+00XX, two bytes of UTF-8 in the output
-    __device__ __forceinline__ void latin1(uint8_t b, bool upper) {
-        if (b < 0x80) {
-            if (upper && b >= 'a' && b <= 'z') b -= 32;
-            if (!upper && b >= 'A' && b <= 'Z') b += 32;
-            put(b);
-        } else {
-            put((uint8_t)(0xC0 | (b >> 6)));
-            put((uint8_t)(0x80 | (b & 0x3F)));
-        }
-    }
-    // String::from_utf8_lossy of s[a, a + k) where s is valid UTF-8: continuation bytes
-    // cut off from their lead are one U+FFFD each; a sequence cut at the end is one
-    __device__ void lossy(const uint8_t* s, uint64_t k) {
-        uint64_t j = 0;
-        while (j < k && (s[j] & 0xC0) == 0x80) {
-            put(0xEF), put(0xBF), put(0xBD);
-            ++j;
-        }
-        while (j < k) {
-            const uint8_t b = s[j];
-            const uint64_t w = b < 0x80 ? 1 : b < 0xE0 ? 2 : b < 0xF0 ? 3 : 4;
-            if (j + w > k) {
-                put(0xEF), put(0xBF), put(0xBD);
-                return;
-            }
-            bytes(s + j, w);
-            j += w;
-        }
-    }
-};
-
-// CIGAR tokenizer of the reference loops: digits accumulate (`is_ascii_digit`), any
-// other char ends a token; `num_buf.parse::<usize>()` fails on an empty buffer or
-// on overflow, and a failed parse skips the op. Multi-byte chars: their lead byte
-// ends the token (an unknown op), their continuation bytes see an empty buffer.
-struct CigarTok {
-    const uint8_t* s;
-    uint64_t n, j = 0;
-    __device__ bool next(uint8_t* op, uint64_t* len) {
-        uint64_t v = 0;
-        bool digits = false, over = false;
-        while (j < n) {
-            const uint8_t c = s[j++];
-            if (c >= '0' && c <= '9') {
-                const uint64_t d = c - '0';
-                if (v > (~0ull - d) / 10) over = true;
-                v = v * 10 + d;
-                digits = true;
-                continue;
-            }
-            if (digits && !over) {
-                *op = c;
-                *len = v;
-                return true;
-            }
-            v = 0;
-            digits = over = false;
-        }
-        return false;
-    }
-};
-
-// ---------------------------------------------------------------- the ops
-template <bool F>
-__device__ void op_revcomp(Emit<F>& o, Str s) {
-    // dna.chars().rev(): whole UTF-8 chars in reverse order, ASCII A/T/C/G/N mapped
-    uint64_t e = s.n;
-    while (e > 0) {
-        uint64_t b = e - 1;
-        while (b > 0 && (s.p[b] & 0xC0) == 0x80) --b;
-        if (e - b == 1) {
-            uint8_t c = s.p[b];
-            c = c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c;
-            o.put(c);
-        } else {
-            o.bytes(s.p + b, e - b);
-        }
-        e = b;
-    }
-}
-
-template <bool F>
-__device__ void op_parse_cigar(Emit<F>& o, Str cig, bool block_dels) {
-    CigarTok t{cig.p, cig.n};
-    uint8_t op;
-    uint64_t len, ref = 0;
-    bool first = true;
-    auto sep = [&] {
-        if (!first) o.put('|');
-        first = false;
-    };
-    while (t.next(&op, &len)) {
-        if (op == 'D') {
-            if (block_dels) {
-                sep();
-                o.put('D'), o.put(','), o.dec(ref), o.put(','), o.dec(len);
-            } else {
-                const uint64_t end = ref + len;  // wrapping, as the release build
-                for (uint64_t p = ref; p < end; ++p) {
-                    sep();
-                    o.put('D'), o.put(','), o.dec(p), o.put(','), o.put('1');
-                }
-            }
-            ref += len;
-        } else if (op == 'I') {
-            sep();
-            o.put('I'), o.put(','), o.dec(ref), o.put(','), o.dec(len);
-        } else {
-            ref += len;
-        }
-    }
-}
-
-// expand_cigar_alignment: side 0 = aligned reference, 1 = aligned query
-template <bool F>
-__device__ void op_aligned(Emit<F>& o, Str ref, Str qry, Str cig, int side) {
-    CigarTok t{cig.p, cig.n};
-    uint8_t op;
-    uint64_t len, rp = 0, qp = 0;
-    while (t.next(&op, &len)) {
-        const uint64_t rk = min(len, ref.n - rp), qk = min(len, qry.n - qp);
-        switch (op) {
-            case 'M':
-            case '=':
-            case 'X':
-                if (side == 0)
-                    for (uint64_t j = 0; j < rk; ++j) o.latin1(ref.p[rp + j], true);
-                else
-                    for (uint64_t j = 0; j < qk; ++j) o.latin1(qry.p[qp + j], true);
-                rp += rk;
-                qp += qk;
-                break;
-            case 'I':
-                if (side == 0)
-                    o.fill('-', len);
-                else
-                    for (uint64_t j = 0; j < qk; ++j) o.latin1(qry.p[qp + j], true);
-                qp += qk;
-                break;
-            case 'D':
-            case 'N':
-                if (side == 0)
-                    for (uint64_t j = 0; j < rk; ++j) o.latin1(ref.p[rp + j], true);
-                else
-                    o.fill('-', len);
-                rp += rk;
-                break;
-            case 'S':
-                if (side == 0)
-                    o.fill('-', len);
-                else
-                    for (uint64_t j = 0; j < qk; ++j) o.latin1(qry.p[qp + j], false);
-                qp += qk;
-                break;
-            default:  // 'H', 'P', unknown
-                break;
-        }
-    }
-}
-
-// extract_insertions_from_cigar: calls fn(ref_pos, seq_pos, len) for every insertion
-// the reference inserts into its HashMap (in walk order; later ones overwrite)
-template <class Fn>
-__device__ void walk_insertions(Str seq, Str cig, Fn&& fn) {
-    CigarTok t{cig.p, cig.n};
-    uint8_t op;
-    uint64_t len, sp = 0, rp = 0;
-    while (t.next(&op, &len)) {
-        switch (op) {
-            case 'M':
-            case '=':
-            case 'X':
-                sp += len;
-                rp += len;
-                break;
-            case 'I':
-                if (sp + len <= seq.n) fn(rp, sp, len);
-                sp += len;
-                break;
-            case 'D':
-            case 'N':
-                rp += len;
-                break;
-            case 'S':
-                sp += len;
-                break;
-            default:
-                break;
-        }
-    }
-}
-
-template <bool F>
-__device__ void op_insertions(Emit<F>& o, Str seq, Str cig) {
-    // map keys ascend in walk order (ref_pos never decreases), so sorting the map is
-    // the walk order with each run of equal keys reduced to its last insertion
-    bool have = false, first = true;
-    uint64_t pr = 0, ps = 0, pl = 0;
-    auto flush = [&] {
-        if (!first) o.put('|');
-        first = false;
-        o.dec(pr);
-        o.put(':');
-        o.lossy(seq.p + ps, pl);
-    };
-    walk_insertions(seq, cig, [&](uint64_t r, uint64_t s, uint64_t l) {
-        if (have && r != pr) flush();
-        have = true;
-        pr = r, ps = s, pl = l;
-    });
-    if (have) flush();
-}
-
-// `str::parse::<usize>()`: optional '+', then >= 1 ASCII digits, no overflow
-__device__ bool parse_usize(const uint8_t* s, uint64_t n, uint64_t* v) {
-    uint64_t j = 0;
-    if (n > 0 && s[0] == '+') j = 1;
-    if (j == n) return false;
-    uint64_t x = 0;
-    for (; j < n; ++j) {
-        const uint8_t c = s[j];
-        if (c < '0' || c > '9') return false;
-        const uint64_t d = c - '0';
-        if (x > (~0ull - d) / 10) return false;
-        x = x * 10 + d;
-    }
-    *v = x;
-    return true;
-}
-
-// the last insertion at ref_pos key (HashMap::get after all inserts)
-__device__ bool find_insertion(Str seq, Str cig, uint64_t key, uint64_t* s_out, uint64_t* l_out) {
-    bool hit = false;
-    walk_insertions(seq, cig, [&](uint64_t r, uint64_t s, uint64_t l) {
-        if (r == key) {
-            hit = true;
-            *s_out = s;
-            *l_out = l;
-        }
-    });
-    return hit;
-}
-
-template <bool F>
-__device__ void op_enrich(Emit<F>& o, Str al, Str seq, Str cig, bool have_ins) {
-    if (!have_ins) {  // seq or CIGAR null: the allele as is
-        o.bytes(al.p, al.n);
-        return;
-    }
-    uint64_t j = 0;
-    while (j < al.n) {
-        const uint8_t c = al.p[j];
-        if (c != '[') {
-            o.put(c);
-            ++j;
-            continue;
-        }
-        uint64_t k = j + 1;
-        while (k < al.n && al.p[k] != ']') ++k;
-        const uint8_t* ct = al.p + j + 1;
-        const uint64_t cn = k - j - 1;
-        o.put('[');
-        o.bytes(ct, cn);
-        if (k == al.n) return;  // no closing bracket: '[' + the rest
-        // "pos:...I" -> the insertion at pos - 1 (or pos): append ":SEQ"
-        uint64_t colon = 0;
-        while (colon < cn && ct[colon] != ':') ++colon;
-        // split_once(':') -> (pos_str, rest); rest.ends_with('I') needs a non-empty rest
-        uint64_t pos;
-        if (colon + 1 < cn && ct[cn - 1] == 'I' && parse_usize(ct, colon, &pos)) {
-            uint64_t s = 0, l = 0;
-            const bool hit =
-                (pos > 0 && find_insertion(seq, cig, pos - 1, &s, &l)) || find_insertion(seq, cig, pos, &s, &l);
-            if (hit) {
-                o.put(':');
-                o.lossy(seq.p + s, l);
-            }
-        }
-        o.put(']');
-        j = k + 1;
-    }
-}
-
-// `phred_char as u8 - base` per char (low 8 bits of the code point, wrapping)
-template <bool F>
-__device__ void op_phred(Emit<F>& o, Str s, uint8_t base, bool as_text) {
-    uint64_t j = 0;
-    bool first = true;
-    while (j < s.n) {
-        const uint8_t b = s.p[j];
-        uint32_t cp;
-        uint64_t w;
-        if (b < 0x80) cp = b, w = 1;
-        else if (b < 0xE0) cp = b & 0x1F, w = 2;
-        else if (b < 0xF0) cp = b & 0x0F, w = 3;
-        else cp = b & 0x07, w = 4;
-        for (uint64_t q = 1; q < w && j + q < s.n; ++q) cp = (cp << 6) | (s.p[j + q] & 0x3F);
-        j += w;
-        const uint8_t v = (uint8_t)((uint8_t)cp - base);
-        if (as_text) {
-            if (!first) o.put('|');
-            o.dec(v);
-        } else {
-            o.put(v);
-        }
-        first = false;
-    }
 }
 
 struct OpArgs {
@@ -410,66 +69,37 @@ struct OpArgs {
     Cols cols;
 };
 
-// Row i of op: false = null output row.
-template <bool F>
-__device__ bool run_row(const OpArgs& a, int64_t i, Emit<F>& o) {
-    const Col* c = a.cols.c;
-    switch (a.op) {
-        case ROGTK_STR_REVCOMP:
-            if (!col_valid(c[0], i)) return false;
-            op_revcomp(o, col_str(c[0], i));
-            return true;
-        case ROGTK_STR_PARSE_CIGAR:
-            if (!col_valid(c[0], i)) return false;
-            op_parse_cigar(o, col_str(c[0], i), a.param != 0);
-            return true;
-        case ROGTK_STR_ALIGNED_REF:
-        case ROGTK_STR_ALIGNED_QUERY:
-            if (!col_valid(c[0], i) || !col_valid(c[1], i) || !col_valid(c[2], i)) return false;
-            op_aligned(o, col_str(c[0], i), col_str(c[1], i), col_str(c[2], i),
-                       a.op == ROGTK_STR_ALIGNED_REF ? 0 : 1);
-            return true;
-        case ROGTK_STR_CIGAR_INSERTIONS:
-            if (!col_valid(c[0], i) || !col_valid(c[1], i)) return false;
-            op_insertions(o, col_str(c[0], i), col_str(c[1], i));
-            return true;
-        case ROGTK_STR_ENRICH_ALLELE: {
-            if (!col_valid(c[0], i)) return false;
-            const bool both = col_valid(c[1], i) && col_valid(c[2], i);
-            const Str none{nullptr, 0};
-            op_enrich(o, col_str(c[0], i), both ? col_str(c[1], i) : none, both ? col_str(c[2], i) : none, both);
-            return true;
-        }
-        case ROGTK_STR_PHRED_STR:
-        case ROGTK_STR_PHRED_LIST:
-            if (!col_valid(c[0], i)) return false;
-            op_phred(o, col_str(c[0], i), (uint8_t)a.param, a.op == ROGTK_STR_PHRED_STR);
-            return true;
-        default:
-            return false;
-    }
-}
+// "row i of column k" of the device columns, for run_row (strings_rows.h)
+struct DevRows {
+    const Col* c;
+    __device__ __forceinline__ bool valid(int k, int64_t i) const { return col_valid(c[k], i); }
+    __device__ __forceinline__ Str str(int k, int64_t i) const { return col_str(c[k], i); }
+};
 
-// lengths[i] = output bytes of row i (0 for null rows); validity bit per row (ballot)
+// lengths[i] = output bytes of row i (0 for null rows; ROGTK_STR_MAX_ROW_BYTES + 1 for a
+// row over the cap, which stays valid); validity bit per row (ballot)
 __global__ __launch_bounds__(kBlock) void k_str_measure(OpArgs a, int64_t* __restrict__ lengths,
                                                         uint64_t* __restrict__ valid_bits) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     bool ok = false;
     if (i < a.n) {
         Emit<false> o{nullptr};
-        ok = run_row(a, i, o);
+        ok = run_row(a.op, a.param, DevRows{a.cols.c}, i, o);
         lengths[i] = ok ? (int64_t)o.n : 0;
     }
     const uint64_t m = __ballot(ok);
     if ((threadIdx.x & 63) == 0 && i < a.n) valid_bits[i >> 6] = m;
 }
 
+// nothing is written for a row that measured over the cap
 __global__ __launch_bounds__(kBlock) void k_str_fill(OpArgs a, const int64_t* __restrict__ offsets,
                                                      uint8_t* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= a.n) return;
-    Emit<true> o{out + offsets[i]};
-    run_row(a, i, o);
+    const int64_t at = offsets[i];
+    if (offsets[i + 1] - at > (int64_t)kRowCap) return;
+    Emit<true> o{out + at};
+    run_row(a.op, a.param, DevRows{a.cols.c}, i, o);
 }
 
 int n_inputs(int op) {
@@ -536,8 +166,9 @@ int rogtk_str_temp_bytes(int64_t n_rows, int64_t* bytes) {
     size_t tb = 0;
     ROGTK_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (const int64_t*)nullptr, (int64_t*)nullptr,
                                                      (int)(n_rows + 1)));
-    // lengths (n + 1 int64) + the scan's own storage
-    *bytes = (int64_t)((n_rows + 1) * 8 + 256 + tb);
+    // lengths (n + 1 int64, padded to 256 B) + the scan's own storage: exactly what
+    // measure asks for, so one byte less is an error there
+    *bytes = (int64_t)(((size_t)(n_rows + 1) * 8 + 255) / 256 * 256 + tb);
     return ROGTK_OK;
 }
 
@@ -647,6 +278,15 @@ int rogtk_str_transform_host(int op, const rogtk_str_col* cols, int n_cols, int6
     ROGTK_HIP_CHECK(hipMemcpyAsync(offs, c->offsets.p, (size_t)(n_rows + 1) * 8, hipMemcpyDeviceToHost, s));
     ROGTK_HIP_CHECK(hipMemcpyAsync(bits, c->bits.p, (size_t)words * 8, hipMemcpyDeviceToHost, s));
     ROGTK_HIP_CHECK(hipStreamSynchronize(s));
+    // a row over the cap (a CIGAR number far beyond its sequences): an error before the
+    // output is allocated or filled
+    for (int64_t r = 0; r < n_rows; ++r)
+        if (offs[r + 1] - offs[r] > ROGTK_STR_MAX_ROW_BYTES) {
+            rogtk_str_result_free(out);
+            set_error("row %lld: the output is longer than ROGTK_STR_MAX_ROW_BYTES (%lld bytes)", (long long)r,
+                      (long long)ROGTK_STR_MAX_ROW_BYTES);
+            return ROGTK_E_UNSUPPORTED;
+        }
     const int64_t total = offs[n_rows];
     out->values = (uint8_t*)malloc((size_t)std::max<int64_t>(total, 1));
     ROGTK_REQUIRE(out->values, ROGTK_E_INVALID, "out of host memory for %lld output bytes", (long long)total);

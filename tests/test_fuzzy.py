@@ -522,3 +522,79 @@ def test_gpu_level1_device_columns(gpu, random_cases):
     got = [data[o[i]:o[i + 1]].decode() if ok[i] else None for i in range(n)]
     assert all(o[i] == o[i + 1] for i in range(n) if not ok[i])
     assert got == want_r.to_pylist() and total == len("".join(x for x in got if x is not None).encode())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [63, 64, 65, 257])
+def test_gpu_level1_device_layouts(gpu, random_cases, n):
+    """The device entry points under the layouts Level 2 never hands them (it uploads int64
+    offsets from 0): int32 and int64 offsets, a first offset that is not 0 inside a larger
+    values buffer, validity at bit offsets 3 and 69; row counts around a wave and a block.
+    contains, replace-measure and replace-fill equal Level 2 on the same rows; the output
+    validity words are rebased to bit 0 with zero bits past n."""
+    torch = gpu
+    c = _pick(random_cases, 32)
+    rows = (list(c["rows"]) * (n // len(c["rows"]) + 1))[:n]
+    for r in range(3, n, 9):
+        rows[r] = None
+    arr = pa.array(rows, type=pa.large_string())
+    prog = FuzzyProgram.native(c["target"], c["wildcard"], c["include_original"], c["max_length"])
+    prog.set_replacement("<<>>")
+    want_m = prog.contains(arr).to_pylist()
+    want_r = prog.replace(arr, True)
+    want_off = np.frombuffer(want_r.buffers()[1], dtype=np.int64, count=n + 1)
+    want_val = want_r.buffers()[2].to_pybytes()[:int(want_off[n])]
+    assert any(want_m) and not all(x for x in want_m if x is not None)
+
+    dev = torch.device("cuda:0")
+    words = (n + 63) // 64
+    canary = 0x5A5A5A5A5A5A5A5A
+    stream = torch.cuda.Stream(device=dev)
+    s = ctypes.c_void_p(stream.cuda_stream)
+    tb = ctypes.c_int64(0)
+    _lib.call("rogtk_str_temp_bytes", n, ctypes.byref(tb))
+    data = [b"zz" if r is None else r.encode() for r in rows]  # null rows own bytes, as Arrow allows
+    for ow, pre, voff in itertools.product((4, 8), (b"", b"\x82\xacPREFIX"), (3, 69)):
+        offs = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum([len(d) for d in data], out=offs[1:])
+        offs += len(pre)
+        bits = np.ones(voff + n + 13, dtype=np.uint8)  # junk outside the column's window
+        bits[:voff] = np.arange(voff) % 3 == 0
+        bits[voff:voff + n] = [r is not None for r in rows]
+        t_off = torch.from_numpy(offs.astype(np.int32 if ow == 4 else np.int64)).to(dev)
+        t_val = torch.from_numpy(np.frombuffer(pre + b"".join(data) + b"\x80POST", dtype=np.uint8).copy()).to(dev)
+        t_bits = torch.from_numpy(np.packbits(bits, bitorder="little")).to(dev)
+        col = _lib.StrCol(t_off.data_ptr(), ow, t_val.data_ptr(), t_val.numel(), t_bits.data_ptr(), voff, n)
+        torch.cuda.synchronize()
+        with torch.cuda.stream(stream):
+            hit = torch.full((words + 1,), canary, dtype=torch.int64, device=dev)
+            vb = torch.full((words + 1,), canary, dtype=torch.int64, device=dev)
+            rvb = torch.full((words + 1,), canary, dtype=torch.int64, device=dev)
+            out_off = torch.full((n + 2,), canary, dtype=torch.int64, device=dev)
+            temp = torch.zeros(tb.value, dtype=torch.uint8, device=dev)
+            _lib.call("rogtk_fuzzy_contains", prog.handle, ctypes.byref(col), hit.data_ptr(), vb.data_ptr(), s)
+            _lib.call("rogtk_fuzzy_replace_measure", prog.handle, ctypes.byref(col), 1, out_off.data_ptr(),
+                      rvb.data_ptr(), temp.data_ptr(), tb.value, s)
+            stream.synchronize()
+            o = out_off.cpu().numpy()
+            total = int(o[n])
+            out = torch.full((total + 64,), 0xA5, dtype=torch.uint8, device=dev)
+            _lib.call("rogtk_fuzzy_replace_fill", prog.handle, ctypes.byref(col), 1, out_off.data_ptr(),
+                      out.data_ptr(), s)
+            stream.synchronize()
+        what = (ow, len(pre), voff)
+        for t in (hit, vb, rvb):
+            assert int(t[words].item()) == canary, what
+        assert o[n + 1] == canary, what
+
+        def unpack(t):
+            return np.unpackbits(t[:words].cpu().numpy().view(np.uint8), bitorder="little")
+
+        valid = [r is not None for r in rows]
+        for t in (vb, rvb):  # rebased to bit 0, zero past n
+            assert unpack(t)[:n].astype(bool).tolist() == valid and not unpack(t)[n:].any(), what
+        h = unpack(hit)
+        assert [bool(x) if v else None for x, v in zip(h[:n], valid)] == want_m, what
+        assert np.array_equal(o[:n + 1], want_off), what
+        data_out = out.cpu().numpy()
+        assert data_out[:total].tobytes() == want_val and (data_out[total:] == 0xA5).all(), what

@@ -12,7 +12,9 @@ import numpy as np
 import pyarrow as pa
 import pytest
 
+import strings_cases as C
 from oracle import pystrings as O
+from strings_cases import _rand_cigar, _rand_dna  # the generators, shared with the other string tests
 
 
 # ------------------------------------------------------------------ oracle KATs
@@ -60,21 +62,6 @@ def test_oracle_revcomp_phred():
 
 
 # ------------------------------------------------------------------ GPU parity
-def _rand_dna(rng, n, lo, hi, alphabet="ACGT"):
-    al = np.frombuffer(alphabet.encode(), np.uint8)
-    return [bytes(rng.choice(al, int(rng.integers(lo, hi + 1)))).decode() for _ in range(n)]
-
-
-def _rand_cigar(rng, qlen, ops="MIDNSHP=X"):
-    parts, used = [], 0
-    while used < qlen:
-        op = ops[int(rng.integers(len(ops)))]
-        k = int(rng.integers(0, 12))
-        parts.append(f"{k}{op}")
-        used += k if op in "MIS=X" else 0
-    return "".join(parts)
-
-
 def _check_strings(got: pa.Array, want):
     assert len(got) == len(want)
     g = got.to_pylist()
@@ -189,3 +176,33 @@ def test_gpu_strings_large_batch(S):
     assert back.equals(arr)
     for i in rng.integers(0, n, 2000):
         assert rc[int(i)].as_py() == O.reverse_complement(bytes(raw[int(i)]).decode())
+
+
+@pytest.mark.gpu
+def test_gpu_known_answers_at_the_limits(S):
+    """strings_cases.KNOWN through the public API: CIGAR numbers at 2^64 - 1 and 2^64 and with
+    leading zeros, lossy cuts of 3- and 4-byte chars, the parse::<usize> corners of enrich,
+    the largest passing neighbours of the over-cap rows. Written answers, not the oracle's."""
+    for c in C.known_cases():
+        op, param, cols, want = c["op"], c["param"], c["cols"], c["want"]
+        if op == "revcomp":
+            got = S.reverse_complement(cols[0])
+        elif op == "parse_cigar":
+            got = S.parse_cigar(cols[0], block_dels=bool(param))
+        elif op == "aligned_ref":
+            got = S.CigarNamespace(cols[0]).align_to_ref(cols[1], cols[2])
+        elif op == "aligned_query":
+            got = S.CigarNamespace(cols[0]).align_to_query(cols[1], cols[2])
+        elif op == "cigar_insertions":
+            got = S.extract_cigar_insertions(cols[0], cols[1])
+        elif op == "enrich":
+            got = S.CigarNamespace(cols[0]).enrich_insertions(cols[1], cols[2])
+        elif op == "phred_str":
+            got = S.phred_to_numeric_str(cols[0], base=param)
+        else:
+            assert op == "phred_list"
+            got, want = S.phred_to_numeric(cols[0], base=param), [w for w in want if w is not None]
+        g = got.to_pylist()
+        assert len(g) == len(want), c["name"]
+        for i, (a, b) in enumerate(zip(g, want)):
+            assert a == b, (c["name"], i, a, b)
