@@ -944,7 +944,9 @@ int rogtk_bam_next(void* reader, int64_t max_records, int mode, int include_sequ
 /* Same, but the batch stays in DEVICE memory (valid until the next call). The decode is
  * enqueued on `stream` without a host wait (the columns' value buffers are sized from
  * host-known bounds; rogtk_bam_check reports corrupt records); NULL: the reader's own
- * stream, synchronised before return (use a real stream for the no-sync path). */
+ * stream, synchronised before return (use a real stream for the no-sync path). As in
+ * rogtk_bam_next, the sequence / quality columns (offsets, values, validity) are NULL
+ * unless asked. */
 int rogtk_bam_next_dev(void* reader, int64_t max_records, int mode, int include_sequence, int include_quality,
                        int64_t* n_records, rogtk_bam_batch* out, void* stream);
 /* The UMI column of a device batch for the H1-H3 engine (config C5): source 0 = the first
@@ -967,9 +969,10 @@ int rogtk_bam_append_strings(const int64_t* src_offsets, const uint8_t* src_valu
                              unsigned long long* overflow, void* stream);
 /* Round 6: k device string columns (int64 offsets from 0, n_i + 1 entries; values; validity
  * bitmaps) concatenated in order into out_offsets (sum n_i + 1), out_values (values_cap
- * bytes; rows past it counted in *overflow, a device u64) and out_validity, with the running
- * byte count in *base (a device int64): no host synchronisation. Arrays of device pointers
- * on the host. */
+ * bytes; rows past it counted in *overflow, a device u64) and out_validity (ceil(sum n_i / 64)
+ * u64 words, bits past the last row zero; none written when there are no rows), with the
+ * running byte count in *base (a device int64): no host synchronisation. Arrays of device
+ * pointers on the host. */
 int rogtk_concat_strings_dev(int k, const int64_t* const* offsets, const uint8_t* const* values,
                              const uint64_t* const* validity, const int64_t* counts, int64_t* out_offsets,
                              uint8_t* out_values, int64_t values_cap, uint64_t* out_validity, int64_t* base,

@@ -1390,13 +1390,17 @@ int rogtk_bam_next_dev(void* reader, int64_t max_records, int mode, int include_
     R->stream = own;
     if (rc != ROGTK_OK) return rc;
     memset(out, 0, sizeof *out);
+    // sequence / quality_scores stay NULL unless asked (as rogtk_bam_next): their lengths are
+    // scanned either way, but their values are not filled and may be one byte long, so the
+    // "no sequence column" guards of rogtk_bam_umi_dev / _append must see NULL
     for (int c = 0; c < 4; ++c) {
+        if ((c == 2 && !include_sequence) || (c == 3 && !include_quality)) continue;
         out->offsets[c] = R->d_off[c].as<int64_t>();
         out->values[c] = R->d_val[c].as<uint8_t>();
     }
     out->validity[1] = R->d_valid[0].as<uint8_t>();
-    out->validity[2] = R->d_valid[3].as<uint8_t>();
-    out->validity[3] = R->d_valid[4].as<uint8_t>();
+    out->validity[2] = include_sequence ? R->d_valid[3].as<uint8_t>() : nullptr;
+    out->validity[3] = include_quality ? R->d_valid[4].as<uint8_t>() : nullptr;
     out->u32[0] = R->d_start.as<uint32_t>();
     out->u32[1] = R->d_end.as<uint32_t>();
     out->u32[2] = R->d_flags.as<uint32_t>();
@@ -1529,7 +1533,8 @@ int rogtk_concat_strings_dev(int k, const int64_t* const* offsets, const uint8_t
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     int64_t n = 0;
     for (int i = 0; i < k; ++i) n += counts[i];
-    ROGTK_HIP_CHECK(hipMemsetAsync(out_validity, 0, (size_t)std::max<int64_t>((n + 63) / 64, 1) * 8, s));
+    // exactly ceil(n / 64) words, as documented: none for an empty result
+    if (n > 0) ROGTK_HIP_CHECK(hipMemsetAsync(out_validity, 0, (size_t)((n + 63) / 64) * 8, s));
     ROGTK_HIP_CHECK(hipMemsetAsync(base, 0, 8, s));
     ROGTK_HIP_CHECK(hipMemsetAsync(overflow, 0, 8, s));
     ROGTK_HIP_CHECK(hipMemsetAsync(out_offsets, 0, 8, s));
