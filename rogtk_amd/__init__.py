@@ -13,6 +13,7 @@ Drop-in surface (mirrors rogtk/__init__.py's `umi` / `hamming` namespaces):
     rg.umi_correct(umis, method="directional")   # count-aware clusters
     rg.umi_correct(umis, method="directional", groups=cell_ids)  # within each key (§4d)
     rg.BarcodeWhitelist(whitelist).correct(cbcs) # whitelist index per row: groups=res.keys (§4e)
+    rg.umi_dedup(umis, 12, score=mapq).keep      # the read to keep per cluster (§4f)
     rg.kmer_spectrum(reads, k=17, min_coverage=20, group_offsets=...)  # H4 (fracture.rs)
     rg.assemble_sequences(group_reads, k=13, min_coverage=1, method="compression")  # H5
     rg.assemble_column_groups(offsets, values, cluster_ids, k=10, min_coverage=5)  # H5, all groups
@@ -47,6 +48,7 @@ from .strings import (  # noqa: F401
 )
 from .correct import UmiCorrection, umi_cluster_summary, umi_correct  # noqa: F401
 from .barcode import BarcodeCorrection, BarcodeNamespace, BarcodeWhitelist, barcode_correct  # noqa: F401
+from .dedup import DedupResult, cluster_best_rows, umi_dedup  # noqa: F401
 from .api import (  # noqa: F401
     FIELDS,
     KMER_STATS,
@@ -73,4 +75,5 @@ __all__ = [
     "phred_to_numeric_str", "phred_to_numeric", "extract_cigar_insertions", "FuzzyNamespace", "FuzzyProgram",
     "umi_correct", "umi_cluster_summary", "UmiCorrection",
     "BarcodeWhitelist", "BarcodeCorrection", "BarcodeNamespace", "barcode_correct",
+    "umi_dedup", "cluster_best_rows", "DedupResult",
 ]

@@ -13,6 +13,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_HERE, "librogtk_hip.so")
 SYNTH_LIB_PATH = os.path.join(_HERE, "_synth", "librogtk_synth.so")
+DEDUP_LIB_PATH = os.path.join(_HERE, "_dedup", "librogtk_dedup.so")
 
 ROGTK_OK = 0
 ROGTK_E_INVALID = 1
@@ -254,6 +255,12 @@ SIGNATURES = {
     "rogtk_barcode_count_dev": [_vp, _vp, _vp, _vp, _i64, _vp, _P_I64, _vp],
     "rogtk_barcode_count_host": [_vp, ctypes.POINTER(StrCol), _vp, _P_I64],
     "rogtk_barcode_set_probe": [_i32],
+    # UMI deduplication: exported by librogtk_dedup.so (dedup())
+    "rogtk_cluster_best_temp_bytes": [_i64, _i64, _P_I64],
+    "rogtk_cluster_best_rows": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    "rogtk_cluster_best_rows_host": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _P_I64],
+    "rogtk_cluster_best_geometry": [_P_I64],
+    "rogtk_cluster_best_set_knobs": [_i32, _i32],
     "rogtk_profile_enable": [_i32],
     "rogtk_profile_select": [ctypes.c_char_p],
     "rogtk_profile_reset": [],
@@ -320,6 +327,30 @@ def hip() -> ctypes.CDLL:
     return _hip
 
 
+DEDUP_PREFIX = "rogtk_cluster_best_"
+_dedup = None
+
+
+def dedup() -> ctypes.CDLL:
+    """Load librogtk_dedup.so (the rogtk_cluster_best_* entries), after librogtk_hip.so, whose
+    error string it shares. Loaded at the feature's first use, not with the package."""
+    global _dedup
+    hip()
+    with _lock:
+        if _dedup is None:
+            if not os.path.exists(DEDUP_LIB_PATH):
+                raise RogtkError(ROGTK_E_NODEVICE, f"{DEDUP_LIB_PATH} is missing: run make -C rogtk_amd/csrc. "
+                                                   "There is no CPU fallback.")
+            lib = ctypes.CDLL(DEDUP_LIB_PATH)
+            for name, argtypes in SIGNATURES.items():
+                if name.startswith(DEDUP_PREFIX):
+                    fn = getattr(lib, name)  # a missing export fails here
+                    fn.argtypes = argtypes
+                    fn.restype = ctypes.c_int
+            _dedup = lib
+    return _dedup
+
+
 def synth() -> ctypes.CDLL:
     global _synth
     with _lock:
@@ -348,7 +379,8 @@ def check(status: int) -> None:
 
 
 def call(name: str, *args) -> None:
-    check(getattr(hip(), name)(*args))
+    lib = dedup() if name.startswith(DEDUP_PREFIX) else hip()
+    check(getattr(lib, name)(*args))
 
 
 def version() -> str:

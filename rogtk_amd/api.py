@@ -347,6 +347,13 @@ class UmiNamespace:
 
         return umi_correct(self._c, umi_len, max_distance, method, groups).corrected
 
+    def dedup(self, umi_len: int = 0, score=None, max_distance: int = 1, method: str = "cluster", groups=None):
+        """Extension (no reference counterpart): the keep mask of UMI deduplication, true for the
+        row with the largest score of its cluster (ties: the first row), DESIGN.md §4f."""
+        from .dedup import umi_dedup
+
+        return umi_dedup(self._c, umi_len, score, max_distance, method, groups).keep
+
 
 class HammingExpr:
     """rogtk/__init__.py:326-349 (`pl.col(..).hamming.*`)."""
