@@ -39,7 +39,7 @@ import numpy as np
 import pyarrow as pa
 
 from . import _lib
-from .columns import ColumnLike, _to_arrow, chunks, concat, validity_buffer
+from .columns import ColumnLike, _one_chunk, chunks, concat, validity_buffer
 
 FIELDS = (
     ("shannon_entropy", pa.float64()),
@@ -223,39 +223,22 @@ def umi_cluster(column: ColumnLike, umi_len: int = 0, max_distance: int = 1, met
     A multi-chunk column is clustered as one batch (ids are global to the column).
     """
     if groups is not None:
-        return _umi_cluster_grouped(column, umi_len, max_distance, method, groups)
-    entry = umi_method_entry(method, max_distance, "rogtk_umi_cluster_host", "rogtk_umi_cluster_directional_host")
-    arr = column
-    if isinstance(arr, pa.ChunkedArray):
-        arr = arr.combine_chunks() if arr.num_chunks else pa.array([], type=arr.type)
-    chs = list(chunks(arr))
-    assert len(chs) == 1
-    ch = chs[0]
+        entry, m = "rogtk_umi_cluster_grouped_host", grouped_method(method, max_distance)
+    else:
+        entry = umi_method_entry(method, max_distance, "rogtk_umi_cluster_host", "rogtk_umi_cluster_directional_host")
+    ch = _one_chunk(column)
     n = ch.n
-    cid = _out(n, np.uint32)
-    nclu = ctypes.c_int64(0)
-    rl = ctypes.c_int(0)
-    o, v, val = ch.ptrs()
-    _lib.call(entry, o, ch.offset_width, v, ch.values.size, val, ch.validity_offset,
-              n, int(umi_len), int(max_distance), _ptr(cid), ctypes.byref(nclu), ctypes.byref(rl))
-    out = pa.Array.from_buffers(pa.uint32(), n, [validity_buffer(ch), pa.py_buffer(cid)])
-    return out, int(nclu.value), int(rl.value)
-
-
-def _umi_cluster_grouped(column, umi_len, max_distance, method, groups):
-    m = grouped_method(method, max_distance)
-    arr = _to_arrow(column)
-    if isinstance(arr, pa.ChunkedArray):
-        arr = arr.combine_chunks() if arr.num_chunks else pa.array([], type=arr.type)
-    ch = next(iter(chunks(arr)))
-    n = ch.n
-    keys = group_keys(groups, n)
     cid = _out(n, np.uint32)
     nclu, rl = ctypes.c_int64(0), ctypes.c_int(0)
+    rule = [int(umi_len), int(max_distance)]
+    tail = []
+    if groups is not None:  # the keys before the rule, the method in it; the clusters' keys are not asked for
+        keys = group_keys(groups, n)
+        rule = [_ptr(keys) if n else None, rule[0], m, rule[1]]
+        tail = [None]
     o, v, val = ch.ptrs()
-    _lib.call("rogtk_umi_cluster_grouped_host", o, ch.offset_width, v, ch.values.size, val, ch.validity_offset, n,
-              _ptr(keys) if n else None, int(umi_len), m, int(max_distance), _ptr(cid), ctypes.byref(nclu),
-              ctypes.byref(rl), None)
+    _lib.call(entry, o, ch.offset_width, v, ch.values.size, val, ch.validity_offset, n, *rule, _ptr(cid),
+              ctypes.byref(nclu), ctypes.byref(rl), *tail)
     out = pa.Array.from_buffers(pa.uint32(), n, [validity_buffer(ch), pa.py_buffer(cid)])
     return out, int(nclu.value), int(rl.value)
 
@@ -272,12 +255,7 @@ def kmer_spectrum(column: ColumnLike, k: int, min_coverage: int, auto_k: bool = 
     kmer_hi / kmer_lo (u64; hi only for k_eff 64), exts (u8), counts (u16),
     entry_offsets (n_groups + 1) and stats (n_groups x 5, columns KMER_STATS).
     """
-    arr = column
-    if isinstance(arr, pa.ChunkedArray):
-        arr = arr.combine_chunks() if arr.num_chunks else pa.array([], type=arr.type)
-    chs = list(chunks(arr))
-    assert len(chs) == 1
-    ch = chs[0]
+    ch = _one_chunk(column)
     n = ch.n
     o, v, val = ch.ptrs()
     cap = ctypes.c_int64(0)

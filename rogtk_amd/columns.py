@@ -67,6 +67,16 @@ def chunks(col: ColumnLike) -> Iterator[HostChunk]:
         yield _chunk(a)
 
 
+def _one_chunk(col: ColumnLike) -> HostChunk:
+    """The column as one batch: what a call whose answer is global to the column takes."""
+    arr = _to_arrow(col)
+    if isinstance(arr, pa.ChunkedArray):
+        arr = arr.combine_chunks() if arr.num_chunks else pa.array([], type=arr.type)
+    chs = list(chunks(arr))
+    assert len(chs) == 1
+    return chs[0]
+
+
 def _chunk(a: pa.Array) -> HostChunk:
     n = len(a)
     bufs = a.buffers()

@@ -27,7 +27,7 @@ import numpy as np
 import pyarrow as pa
 
 from . import _lib
-from .columns import ColumnLike, _to_arrow, chunks, validity_buffer
+from .columns import ColumnLike, _one_chunk, validity_buffer
 
 CLUSTER_FIELDS = ("representative", "n_reads", "n_distinct")
 
@@ -39,16 +39,6 @@ class UmiCorrection:
     n_clusters: int
     clusters: pa.StructArray
     umi_len: int = 0
-
-
-def _one_chunk(column: ColumnLike):
-    """The column as one batch (the clusters are global to the column)."""
-    arr = _to_arrow(column)
-    if isinstance(arr, pa.ChunkedArray):
-        arr = arr.combine_chunks() if arr.num_chunks else pa.array([], type=arr.type)
-    chs = list(chunks(arr))
-    assert len(chs) == 1
-    return chs[0]
 
 
 def _desc(ch) -> _lib.StrCol:
@@ -87,41 +77,6 @@ def _clusters(reps, n_reads, n_distinct, typ) -> pa.StructArray:
                                       names=list(CLUSTER_FIELDS))
 
 
-def _umi_correct_grouped(column, umi_len, max_distance, method, groups) -> UmiCorrection:
-    from .api import group_keys, grouped_method
-
-    m = grouped_method(method, max_distance)
-    ch = _one_chunk(column)
-    n = ch.n
-    keys = group_keys(groups, n)
-    cid = np.zeros(max(n, 1), dtype=np.uint32)
-    corrected, reps = _lib.StrResult(), _lib.StrResult()
-    n_reads, n_distinct, cgroup = _lib.U32Result(), _lib.U32Result(), _lib.U32Result()
-    nclu, rl = ctypes.c_int64(0), ctypes.c_int(0)
-    desc = _desc(ch)
-    lib = _lib.hip()
-    _lib.check(lib.rogtk_umi_correct_grouped_host(
-        ctypes.byref(desc), ctypes.c_void_p(keys.ctypes.data) if n else None, int(umi_len), m, int(max_distance),
-        ctypes.c_void_p(cid.ctypes.data), ctypes.byref(corrected), ctypes.byref(reps), ctypes.byref(n_reads),
-        ctypes.byref(n_distinct), ctypes.byref(cgroup), ctypes.byref(nclu), ctypes.byref(rl)))
-    try:
-        typ = _text_type(ch)
-        out = _take_str(corrected, typ)
-        k = int(nclu.value)
-        group = (np.ctypeslib.as_array(ctypes.cast(cgroup.data, ctypes.POINTER(ctypes.c_uint32)), (k,)).copy()
-                 if k else np.zeros(0, np.uint32))
-        clusters = pa.StructArray.from_arrays(
-            [_take_str(reps, typ), _take_u32(n_reads), _take_u32(n_distinct), pa.array(group, type=pa.uint32())],
-            names=list(CLUSTER_FIELDS) + ["group"])
-    finally:
-        lib.rogtk_str_result_free(ctypes.byref(corrected))
-        lib.rogtk_str_result_free(ctypes.byref(reps))
-        for r in (n_reads, n_distinct, cgroup):
-            lib.rogtk_u32_result_free(ctypes.byref(r))
-    ids = pa.Array.from_buffers(pa.uint32(), n, [validity_buffer(ch), pa.py_buffer(cid[:n])])
-    return UmiCorrection(out, ids, int(nclu.value), clusters, int(rl.value))
-
-
 def umi_correct(column: ColumnLike, umi_len: int = 0, max_distance: int = 1,
                 method: str = "cluster", groups=None) -> UmiCorrection:
     """Clusters of the column (as ``umi_cluster``: method="cluster" the H3 components,
@@ -129,32 +84,41 @@ def umi_correct(column: ColumnLike, umi_len: int = 0, max_distance: int = 1,
     UMI of every row. A multi-chunk column is one batch. groups (one unsigned 32-bit key per
     row): clusters form within each key, and ``clusters`` gains a fourth field
     ``group``, the key of every cluster."""
-    if groups is not None:
-        return _umi_correct_grouped(column, umi_len, max_distance, method, groups)
-    from .api import umi_method_entry
+    from .api import group_keys, grouped_method, umi_method_entry
 
-    entry = umi_method_entry(method, max_distance, "rogtk_umi_correct_host", "rogtk_umi_correct_directional_host")
+    grouped = groups is not None
+    if grouped:
+        entry, m = "rogtk_umi_correct_grouped_host", grouped_method(method, max_distance)
+    else:
+        entry = umi_method_entry(method, max_distance, "rogtk_umi_correct_host", "rogtk_umi_correct_directional_host")
     ch = _one_chunk(column)
     n = ch.n
     cid = np.zeros(max(n, 1), dtype=np.uint32)
     corrected, reps = _lib.StrResult(), _lib.StrResult()
-    n_reads, n_distinct = _lib.U32Result(), _lib.U32Result()
+    n_reads, n_distinct, cgroup = _lib.U32Result(), _lib.U32Result(), _lib.U32Result()
     nclu, rl = ctypes.c_int64(0), ctypes.c_int(0)
+    rule = [int(umi_len), int(max_distance)]
+    outs = [ctypes.byref(r) for r in (corrected, reps, n_reads, n_distinct)]
+    if grouped:  # the keys before the rule, the method in it, the clusters' keys after the tables
+        keys = group_keys(groups, n)
+        rule = [ctypes.c_void_p(keys.ctypes.data) if n else None, rule[0], m, rule[1]]
+        outs.append(ctypes.byref(cgroup))
     desc = _desc(ch)
     lib = _lib.hip()
-    _lib.check(getattr(lib, entry)(ctypes.byref(desc), int(umi_len), int(max_distance),
-                                   ctypes.c_void_p(cid.ctypes.data), ctypes.byref(corrected),
-                                   ctypes.byref(reps), ctypes.byref(n_reads), ctypes.byref(n_distinct),
+    _lib.check(getattr(lib, entry)(ctypes.byref(desc), *rule, ctypes.c_void_p(cid.ctypes.data), *outs,
                                    ctypes.byref(nclu), ctypes.byref(rl)))
     try:
         typ = _text_type(ch)
         out = _take_str(corrected, typ)
         clusters = _clusters(reps, n_reads, n_distinct, typ)
+        if grouped:
+            clusters = pa.StructArray.from_arrays(clusters.flatten() + [_take_u32(cgroup)],
+                                                  names=list(CLUSTER_FIELDS) + ["group"])
     finally:
         lib.rogtk_str_result_free(ctypes.byref(corrected))
         lib.rogtk_str_result_free(ctypes.byref(reps))
-        lib.rogtk_u32_result_free(ctypes.byref(n_reads))
-        lib.rogtk_u32_result_free(ctypes.byref(n_distinct))
+        for r in (n_reads, n_distinct, cgroup):
+            lib.rogtk_u32_result_free(ctypes.byref(r))
     ids = pa.Array.from_buffers(pa.uint32(), n, [validity_buffer(ch), pa.py_buffer(cid[:n])])
     return UmiCorrection(out, ids, int(nclu.value), clusters, int(rl.value))
 

@@ -26,6 +26,7 @@
 #include <atomic>
 
 #include "column_util.h"
+#include "level2.h"
 
 namespace rogtk {
 namespace {
@@ -485,10 +486,10 @@ int barcode_whitelist_build(const uint64_t* host_codes, int64_t W, int L, void**
     return ROGTK_OK;
 }
 
-int barcode_correct(const void* handle, const void* offsets, int ow, const uint8_t* values, const uint8_t* validity,
-                    int64_t voff, int64_t n, int ambiguous, const uint32_t* prior_counts, uint32_t* index,
+int barcode_correct(const void* handle, const DevCol& col, int ambiguous, const uint32_t* prior_counts, uint32_t* index,
                     uint8_t* status, uint32_t* exact_counts, uint32_t* counts, bool count_only, int64_t* totals5,
                     hipStream_t s) {
+    const auto [offsets, ow, values, validity, voff, n] = col;
     const Whitelist* w = (const Whitelist*)handle;
     if (int rc = check_device(w)) return rc;
     const int64_t W = w->W;

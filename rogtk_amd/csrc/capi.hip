@@ -1,9 +1,11 @@
-// capi.hip — extern "C" surface of librogtk_hip.so (declared in include/rogtk_hip.h).
+// capi.hip — extern "C" surface of librogtk_hip.so (declared in include/rogtk_hip.h), but for the
+// UMI cluster / correct family (umi_api.hip) and the entries that live next to their kernels.
 //
 // Host-side responsibilities: argument validation, thread-local last-error,
 // the glibc-log2 entropy tables (bit-exact with the reference's f64::log2),
-// Hamming target encoding, the per-thread device context of the level-2
-// (host Arrow buffer) entry points, and launch-bracketing profiling events.
+// Hamming target encoding, launch-bracketing profiling events, and the definitions of what
+// level2.h declares: the per-thread device context of the level-2 (host Arrow buffer) entry
+// points, the upload of a host column and the checks those entries share.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,7 +20,7 @@
 #include <thread>
 #include <vector>
 
-#include "rogtk_internal.h"
+#include "level2.h"
 
 namespace rogtk {
 
@@ -329,8 +331,6 @@ using namespace rogtk;
 
 namespace {
 
-inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 int check_offset_width(int ow) {
     ROGTK_REQUIRE(ow == 4 || ow == 8, ROGTK_E_INVALID, "offset_width must be 4 or 8, got %d", ow);
     return ROGTK_OK;
@@ -346,13 +346,7 @@ int check_packed_alignment(const uint32_t* codes, const ScoreOut& o, const uint3
     return ROGTK_OK;
 }
 
-// --------------------------------------------- per-thread level-2 context
-// Host <-> device transfers of the level-2 entry points. Pinned host memory
-// (hipHostMalloc / rogtk_host_alloc / hipHostRegister) moves by direct DMA. Pageable
-// memory moves through two pinned staging buffers of the context, chunk by chunk, so
-// the DMA of one chunk overlaps the host copy of the other; the host copies of a chunk
-// are split over a few threads (a single thread's memcpy, and the first-touch page
-// faults of a fresh destination, cap a pageable copy well below the PCIe link).
+// --------------------------------------------- per-thread level-2 context (level2.h)
 constexpr size_t kStageChunk = (size_t)32 << 20;
 
 int host_copy_threads() {
@@ -390,79 +384,85 @@ bool is_pinned(const void* p) {
     return a.type == hipMemoryTypeHost;
 }
 
-struct HostCtx {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    DevBuf offsets, values, validity, codes, regbits, irr, nirr, target, out[8], ws, bitmap;
-    DevBuf grp[2];  // the grouped entries: the rows' keys, the clusters' keys
-    int64_t ws_L = -1, ws_maxd = -1;
-    void* pin[2] = {nullptr, nullptr};  // staging for pageable host memory
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~HostCtx() {
-        for (int k = 0; k < 2; ++k) {
-            if (pin[k]) hipHostFree(pin[k]);
-            if (ev[k]) hipEventDestroy(ev[k]);
-        }
-        if (stream) hipStreamDestroy(stream);
+thread_local std::unique_ptr<HostCtx> t_ctx;
+
+// Longest row of a device column (irregular rows' radix-sort / byte-path width).
+template <class O>
+__global__ void k_max_len(const O* __restrict__ off, int64_t n, unsigned long long* out) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long m = 0;
+    if (r < n) m = (unsigned long long)((int64_t)off[r + 1] - (int64_t)off[r]);
+    for (int d = 32; d; d >>= 1) m = max(m, (unsigned long long)__shfl_xor(m, d));
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
+}
+
+}  // namespace
+
+namespace rogtk {
+
+HostCtx::~HostCtx() {
+    for (int k = 0; k < 2; ++k) {
+        if (pin[k]) hipHostFree(pin[k]);
+        if (ev[k]) hipEventDestroy(ev[k]);
     }
-    int staging() {
-        for (int k = 0; k < 2; ++k) {
-            if (!pin[k]) ROGTK_HIP_CHECK(hipHostMalloc(&pin[k], kStageChunk, hipHostMallocDefault));
-            if (!ev[k]) ROGTK_HIP_CHECK(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
-        }
-        return ROGTK_OK;
+    if (stream) hipStreamDestroy(stream);
+}
+
+int HostCtx::staging() {
+    for (int k = 0; k < 2; ++k) {
+        if (!pin[k]) ROGTK_HIP_CHECK(hipHostMalloc(&pin[k], kStageChunk, hipHostMallocDefault));
+        if (!ev[k]) ROGTK_HIP_CHECK(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
     }
-    // device -> host; complete on return
-    int d2h(void* dst, const void* src, size_t bytes) {
-        if (bytes == 0) return ROGTK_OK;
-        if (is_pinned(dst)) {
-            ROGTK_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream));
-            ROGTK_HIP_CHECK(hipStreamSynchronize(stream));
-            return ROGTK_OK;
-        }
-        if (int rc = staging()) return rc;
-        size_t prev_off = 0, prev_len = 0;
-        int k = 0;
-        for (size_t off = 0; off < bytes; off += kStageChunk, k ^= 1) {
-            const size_t len = std::min(kStageChunk, bytes - off);
-            ROGTK_HIP_CHECK(hipMemcpyAsync(pin[k], (const uint8_t*)src + off, len, hipMemcpyDeviceToHost, stream));
-            ROGTK_HIP_CHECK(hipEventRecord(ev[k], stream));
-            if (off > 0) {  // the previous chunk: out of its staging buffer while this one moves
-                ROGTK_HIP_CHECK(hipEventSynchronize(ev[k ^ 1]));
-                par_memcpy((uint8_t*)dst + prev_off, pin[k ^ 1], prev_len);
-            }
-            prev_off = off;
-            prev_len = len;
-        }
-        ROGTK_HIP_CHECK(hipEventSynchronize(ev[k ^ 1]));
-        par_memcpy((uint8_t*)dst + prev_off, pin[k ^ 1], prev_len);
-        return ROGTK_OK;
-    }
-    // host -> device; enqueued on the stream (the host buffer may be reused on return)
-    int h2d(void* dst, const void* src, size_t bytes) {
-        if (bytes == 0) return ROGTK_OK;
-        if (is_pinned(src)) {
-            ROGTK_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream));
-            return ROGTK_OK;
-        }
-        if (int rc = staging()) return rc;
-        int k = 0;
-        int64_t i = 0;
-        for (size_t off = 0; off < bytes; off += kStageChunk, k ^= 1, ++i) {
-            const size_t len = std::min(kStageChunk, bytes - off);
-            if (i >= 2) ROGTK_HIP_CHECK(hipEventSynchronize(ev[k]));  // its DMA of two chunks ago is done
-            par_memcpy(pin[k], (const uint8_t*)src + off, len);
-            ROGTK_HIP_CHECK(hipMemcpyAsync((uint8_t*)dst + off, pin[k], len, hipMemcpyHostToDevice, stream));
-            ROGTK_HIP_CHECK(hipEventRecord(ev[k], stream));
-        }
-        // the staging buffers are reused by the next transfer only after these DMAs: every
-        // later use first waits on the events above (or the stream is synchronised)
+    return ROGTK_OK;
+}
+
+int HostCtx::d2h(void* dst, const void* src, size_t bytes) {
+    if (bytes == 0) return ROGTK_OK;
+    if (is_pinned(dst)) {
+        ROGTK_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream));
         ROGTK_HIP_CHECK(hipStreamSynchronize(stream));
         return ROGTK_OK;
     }
-};
+    if (int rc = staging()) return rc;
+    size_t prev_off = 0, prev_len = 0;
+    int k = 0;
+    for (size_t off = 0; off < bytes; off += kStageChunk, k ^= 1) {
+        const size_t len = std::min(kStageChunk, bytes - off);
+        ROGTK_HIP_CHECK(hipMemcpyAsync(pin[k], (const uint8_t*)src + off, len, hipMemcpyDeviceToHost, stream));
+        ROGTK_HIP_CHECK(hipEventRecord(ev[k], stream));
+        if (off > 0) {  // the previous chunk: out of its staging buffer while this one moves
+            ROGTK_HIP_CHECK(hipEventSynchronize(ev[k ^ 1]));
+            par_memcpy((uint8_t*)dst + prev_off, pin[k ^ 1], prev_len);
+        }
+        prev_off = off;
+        prev_len = len;
+    }
+    ROGTK_HIP_CHECK(hipEventSynchronize(ev[k ^ 1]));
+    par_memcpy((uint8_t*)dst + prev_off, pin[k ^ 1], prev_len);
+    return ROGTK_OK;
+}
 
-thread_local std::unique_ptr<HostCtx> t_ctx;
+int HostCtx::h2d(void* dst, const void* src, size_t bytes) {
+    if (bytes == 0) return ROGTK_OK;
+    if (is_pinned(src)) {
+        ROGTK_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream));
+        return ROGTK_OK;
+    }
+    if (int rc = staging()) return rc;
+    int k = 0;
+    int64_t i = 0;
+    for (size_t off = 0; off < bytes; off += kStageChunk, k ^= 1, ++i) {
+        const size_t len = std::min(kStageChunk, bytes - off);
+        if (i >= 2) ROGTK_HIP_CHECK(hipEventSynchronize(ev[k]));  // its DMA of two chunks ago is done
+        par_memcpy(pin[k], (const uint8_t*)src + off, len);
+        ROGTK_HIP_CHECK(hipMemcpyAsync((uint8_t*)dst + off, pin[k], len, hipMemcpyHostToDevice, stream));
+        ROGTK_HIP_CHECK(hipEventRecord(ev[k], stream));
+    }
+    // the staging buffers are reused by the next transfer only after these DMAs: every
+    // later use first waits on the events above (or the stream is synchronised)
+    ROGTK_HIP_CHECK(hipStreamSynchronize(stream));
+    return ROGTK_OK;
+}
 
 int host_ctx(HostCtx** out) {
     int n = 0;
@@ -481,46 +481,6 @@ int host_ctx(HostCtx** out) {
     return ROGTK_OK;
 }
 
-struct HostCol {
-    const void* offsets;
-    int ow;
-    const uint8_t* values;
-    int64_t values_len;
-    const uint8_t* validity;
-    int64_t voff;
-    int64_t n;
-    int64_t off0() const { return ow == 4 ? ((const int32_t*)offsets)[0] : ((const int64_t*)offsets)[0]; }
-    int64_t off(int64_t i) const {
-        return ow == 4 ? ((const int32_t*)offsets)[i] : ((const int64_t*)offsets)[i];
-    }
-    bool valid(int64_t i) const {
-        if (!validity) return true;
-        const int64_t b = voff + i;
-        return (validity[b >> 3] >> (b & 7)) & 1;
-    }
-    int first_len() const {
-        for (int64_t i = 0; i < n; ++i)
-            if (valid(i)) return (int)std::min<int64_t>(off(i + 1) - off(i), 1 << 30);
-        return 0;
-    }
-    int64_t max_len() const {
-        int64_t m = 0;
-        for (int64_t i = 0; i < n; ++i) m = std::max<int64_t>(m, off(i + 1) - off(i));
-        return m;
-    }
-};
-
-// Longest row of a device column (irregular rows' radix-sort / byte-path width).
-template <class O>
-__global__ void k_max_len(const O* __restrict__ off, int64_t n, unsigned long long* out) {
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned long long m = 0;
-    if (r < n) m = (unsigned long long)((int64_t)off[r + 1] - (int64_t)off[r]);
-    for (int d = 32; d; d >>= 1) m = max(m, (unsigned long long)__shfl_xor(m, d));
-    if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
-}
-
-// the longest row of a device column of n >= 1 rows, reduced into the zeroed device word `slot`
 int launch_max_len(const void* offsets, int ow, int64_t n, unsigned long long* slot, hipStream_t s) {
     const dim3 g((unsigned)((n + 255) / 256));
     if (ow == 4)
@@ -531,7 +491,6 @@ int launch_max_len(const void* offsets, int ow, int64_t n, unsigned long long* s
     return ROGTK_OK;
 }
 
-// the same with the word zeroed first and read back: *out on the host (one sync of s)
 int column_max_len(const void* offsets, int ow, int64_t n, unsigned long long* slot, hipStream_t s, int64_t* out) {
     ROGTK_HIP_CHECK(hipMemsetAsync(slot, 0, 8, s));
     if (int rc = launch_max_len(offsets, ow, n, slot, s)) return rc;
@@ -542,14 +501,11 @@ int column_max_len(const void* offsets, int ow, int64_t n, unsigned long long* s
     return ROGTK_OK;
 }
 
-// the same for the column already uploaded to c->offsets
 int device_max_len(HostCtx* c, int ow, int64_t n, int64_t* out) {
     if (int rc = c->nirr.ensure(16)) return rc;
     return column_max_len(c->offsets.p, ow, n, c->nirr.as<unsigned long long>() + 1, c->stream, out);
 }
 
-// the size limits shared by the entries that take rows and cluster ids (an entry without a
-// cluster count passes 0)
 int check_rows_and_clusters(const char* name, int64_t n, int64_t n_clusters) {
     ROGTK_REQUIRE(n >= 0 && n < (1ll << 31), ROGTK_E_UNSUPPORTED, "%s: n %lld outside 0..2^31-1", name, (long long)n);
     ROGTK_REQUIRE(n_clusters >= 0 && n_clusters < (1ll << 32) - 1, ROGTK_E_INVALID, "%s: bad n_clusters %lld", name,
@@ -557,43 +513,36 @@ int check_rows_and_clusters(const char* name, int64_t n, int64_t n_clusters) {
     return ROGTK_OK;
 }
 
-// Upload a host column and stage it; returns the resolved packed length in *L.
-int upload_and_stage(HostCtx* c, const HostCol& h, int L_req, int* L_out, int64_t* n_irr_host) {
+int upload_col(HostCtx* c, const HostCol& h) {
     const int64_t n = h.n;
-    const int ow = h.ow;
-    ROGTK_REQUIRE(c->offsets.ensure((size_t)(n + 1) * ow) == ROGTK_OK, ROGTK_E_HIP, "%s", rogtk_last_error());
-    if (int rc = c->h2d(c->offsets.p, h.offsets, (size_t)(n + 1) * ow)) return rc;
-    // values: upload [0, off(n)) so the device offsets stay valid as given
-    const int64_t vbytes = std::max<int64_t>(h.off(n), 1);
     ROGTK_REQUIRE(h.off(n) <= h.values_len || h.values_len < 0, ROGTK_E_INVALID,
-                  "offsets reference %lld bytes but values_len is %lld", (long long)h.off(n),
-                  (long long)h.values_len);
-    if (c->values.ensure((size_t)vbytes) != ROGTK_OK) return ROGTK_E_HIP;
-    if (h.off(n) > 0)
-        if (int rc = c->h2d(c->values.p, h.values, (size_t)h.off(n))) return rc;
-    const uint8_t* dvalid = nullptr;
+                  "offsets reference %lld bytes but values_len is %lld", (long long)h.off(n), (long long)h.values_len);
+    if (int rc = c->offsets.ensure((size_t)(n + 1) * h.ow)) return rc;
+    if (int rc = c->h2d(c->offsets.p, h.offsets, (size_t)(n + 1) * h.ow)) return rc;
+    // values: [0, off(n)), so the device offsets stay valid as given
+    if (int rc = c->values.ensure((size_t)std::max<int64_t>(h.off(n), 1))) return rc;
+    if (int rc = c->h2d(c->values.p, h.values, (size_t)h.off(n))) return rc;
     if (h.validity) {
         const size_t vb = (size_t)((h.voff + n + 7) / 8);
-        if (c->validity.ensure(vb) != ROGTK_OK) return ROGTK_E_HIP;
+        if (int rc = c->validity.ensure(vb)) return rc;
         if (int rc = c->h2d(c->validity.p, h.validity, vb)) return rc;
-        dvalid = c->validity.as<uint8_t>();
     }
-    int L = L_req > 0 ? L_req : h.first_len();
-    *L_out = L;
-    const int64_t words = (n + 63) / 64;
+    return ROGTK_OK;
+}
+
+int stage_uploaded(HostCtx* c, const DevCol& col, int L, int64_t* n_irr, hipStream_t s) {
+    const int64_t n = col.n, words = (n + 63) / 64;
     if (c->codes.ensure((size_t)std::max<int64_t>(n, 4) * 4) != ROGTK_OK ||
         c->regbits.ensure((size_t)std::max<int64_t>(words, 1) * 8) != ROGTK_OK ||
-        c->irr.ensure((size_t)std::max<int64_t>(n, 1) * 8) != ROGTK_OK ||
-        c->nirr.ensure(16) != ROGTK_OK)
+        c->irr.ensure((size_t)std::max<int64_t>(n, 1) * 8) != ROGTK_OK || c->nirr.ensure(16) != ROGTK_OK)
         return ROGTK_E_HIP;
-    ROGTK_HIP_CHECK(hipMemsetAsync(c->nirr.p, 0, 8, c->stream));
-    int rc = launch_stage(c->offsets.p, ow, c->values.as<uint8_t>(), dvalid, h.voff, n, L,
-                          c->codes.as<uint32_t>(), c->regbits.as<uint64_t>(), c->irr.as<int64_t>(),
-                          c->nirr.as<unsigned long long>(), c->stream);
-    if (rc) return rc;
-    if (n_irr_host) {
-        ROGTK_HIP_CHECK(hipMemcpyAsync(n_irr_host, c->nirr.p, 8, hipMemcpyDeviceToHost, c->stream));
-        ROGTK_HIP_CHECK(hipStreamSynchronize(c->stream));
+    ROGTK_HIP_CHECK(hipMemsetAsync(c->nirr.p, 0, 16, s));
+    if (int rc = launch_stage(col.offsets, col.ow, col.values, col.validity, col.voff, n, L, c->codes.as<uint32_t>(),
+                              c->regbits.as<uint64_t>(), c->irr.as<int64_t>(), c->nirr.as<unsigned long long>(), s))
+        return rc;
+    if (n_irr) {
+        ROGTK_HIP_CHECK(hipMemcpyAsync(n_irr, c->nirr.p, 8, hipMemcpyDeviceToHost, s));
+        ROGTK_HIP_CHECK(hipStreamSynchronize(s));
     }
     return ROGTK_OK;
 }
@@ -608,7 +557,19 @@ int check_host_col(const HostCol& h) {
     return ROGTK_OK;
 }
 
-}  // namespace
+int empty_str_result(int64_t n, rogtk_str_result* out) {
+    const int64_t words = std::max<int64_t>((n + 63) / 64, 1);
+    out->n = n;
+    out->offsets = (int64_t*)calloc((size_t)n + 1, 8);
+    out->values = (uint8_t*)calloc(1, 1);
+    out->validity = (uint8_t*)calloc((size_t)words, 8);
+    out->values_len = 0;
+    out->null_count = 0;
+    ROGTK_REQUIRE(out->offsets && out->values && out->validity, ROGTK_E_INVALID, "out of host memory");
+    return ROGTK_OK;
+}
+
+}  // namespace rogtk
 
 namespace rogtk {
 namespace detail_attach {
@@ -932,9 +893,10 @@ int rogtk_umi_complexity_host(const void* offsets, int offset_width, const uint8
     if (n == 0) return ROGTK_OK;
     HostCtx* c;
     if (int rc = host_ctx(&c)) return rc;
-    int L = 0;
+    if (int rc = upload_col(c, h)) return rc;
+    const int L = h.first_len();
     int64_t n_irr = 0;
-    if (int rc = upload_and_stage(c, h, 0, &L, &n_irr)) return rc;
+    if (int rc = stage_uploaded(c, DevCol(c, h), L, &n_irr, c->stream)) return rc;
     int64_t max_len = 0;  // only the byte path (irregular rows) needs it
     if (n_irr > 0)
         if (int rc = device_max_len(c, offset_width, n, &max_len)) return rc;
@@ -986,9 +948,10 @@ int rogtk_hamming_host(const void* offsets, int offset_width, const uint8_t* val
     const uint8_t* tg = target ? target : &kEmpty;
     HostCtx* c;
     if (int rc = host_ctx(&c)) return rc;
-    int L = 0;
+    if (int rc = upload_col(c, h)) return rc;
+    const int L = h.first_len();
     int64_t n_irr = 0;
-    if (int rc = upload_and_stage(c, h, 0, &L, &n_irr)) return rc;
+    if (int rc = stage_uploaded(c, DevCol(c, h), L, &n_irr, c->stream)) return rc;
     int64_t max_len = 0;  // only the byte path (irregular rows) needs it
     if (n_irr > 0)
         if (int rc = device_max_len(c, offset_width, n, &max_len)) return rc;
@@ -1023,725 +986,13 @@ int rogtk_hamming_host(const void* offsets, int offset_width, const uint8_t* val
     return ROGTK_OK;
 }
 
-namespace {
-
-
-// H3 over a column already staged into c->codes / regbits / irr (n_irr irregular rows):
-// regular rows through the cluster engine, then the irregular rows (exact bytes, or for
-// max_distance 1 their Hamming-1 edges merged with the regular clusters, irregular.hip);
-// ids into did (device), on stream s.
-int cluster_staged(HostCtx* c, const void* d_offsets, int ow, const uint8_t* d_values, const uint8_t* d_validity,
-                   int64_t voff, int64_t n, int L, int64_t n_irr, int64_t max_len, int max_distance, uint32_t* did,
-                   int64_t* n_clusters, hipStream_t s) {
-    if (L > kMaxPackedLen && L <= 32)  // long UMIs: sort-based engine (regular + irregular rows)
-        return long_cluster(d_offsets, ow, d_values, d_validity, voff, n, L, max_distance, max_len, did, n_clusters, s);
-    int64_t n_reg_clusters = 0;
-    const int64_t* stats_dev = nullptr;
-    if (L >= 1 && L <= kMaxPackedLen) {
-        const int64_t space = (int64_t)1 << std::min(2 * L, 40);
-        const int64_t maxd = std::max<int64_t>(1, std::min<int64_t>(space, n));
-        ClusterLayout cl;
-        if (int rc = cluster_layout(L, maxd, &cl)) return rc;
-        if (c->ws_L != L || c->ws_maxd < cl.max_distinct) {
-            if (int rc = c->ws.ensure((size_t)cl.total)) return rc;
-            if (int rc = rogtk_cluster_init(c->ws.p, L, cl.max_distinct, s)) return rc;
-            c->ws_L = L;
-            c->ws_maxd = cl.max_distinct;
-        }
-        ClusterLayout use;
-        cluster_layout(L, c->ws_maxd, &use);
-        if (int rc = c->bitmap.ensure((size_t)use.words * 8)) return rc;
-        int rc = rogtk_cluster_mark(c->codes.as<uint32_t>(), c->regbits.as<uint64_t>(), n, L, c->ws.p,
-                                    use.max_distinct, s);
-        if (!rc) rc = rogtk_cluster_local_bitmap(c->ws.p, L, use.max_distinct, c->bitmap.as<uint64_t>(), s);
-        if (!rc) rc = rogtk_cluster_resolve(c->ws.p, L, use.max_distinct, c->bitmap.as<uint64_t>(), 1,
-                                            max_distance, s);
-        if (!rc) rc = rogtk_cluster_assign(c->ws.p, L, use.max_distinct, c->codes.as<uint32_t>(),
-                                           c->regbits.as<uint64_t>(), n, did, s);
-        if (rc) {
-            c->ws_L = -1;  // presence may be dirty: re-initialise on the next call
-            return rc;
-        }
-        int64_t st[4];
-        if (int rc2 = rogtk_cluster_stats(c->ws.p, L, use.max_distinct, st, s)) return rc2;
-        ROGTK_REQUIRE(st[2] == 0, ROGTK_E_OVERFLOW, "cluster: distinct UMIs exceeded max_distinct");
-        n_reg_clusters = st[1];
-        stats_dev = (const int64_t*)((uint8_t*)c->ws.p + use.off_stats);
-    } else {
-        ROGTK_HIP_CHECK(hipMemsetAsync(did, 0xFF, (size_t)n * 4, s));
-    }
-    int64_t total = n_reg_clusters;
-    if (n_irr > 0 && max_distance == 1) {
-        // Hamming-1 edges of the irregular rows (to each other and to regular codes)
-        const bool packable = L >= 1 && L <= kMaxPackedLen;
-        ClusterLayout use{};
-        if (packable) cluster_layout(L, c->ws_maxd, &use);
-        const uint8_t* ws = (const uint8_t*)c->ws.p;
-        CodeLookup lk = [&](const uint64_t* q, int64_t nq, uint32_t* lab, hipStream_t st) {
-            return launch_cluster_lookup(use, ws, q, nq, lab, st);
-        };
-        int rc = irregular_merge(d_offsets, ow, d_values, c->irr.as<int64_t>(), n_irr, max_len, L, n_reg_clusters,
-                                 packable ? &lk : nullptr, did, n, did, &total, s);
-        if (rc) return rc;
-    } else if (n_irr > 0) {
-        int64_t n_irr_clusters = 0;
-        int rc = irregular_cluster(d_offsets, ow, d_values, c->irr.as<int64_t>(), n_irr, max_len, stats_dev, did,
-                                   &n_irr_clusters, s);
-        if (rc) return rc;
-        total += n_irr_clusters;
-    }
-    if (n_clusters) *n_clusters = total;
-    return ROGTK_OK;
-}
-
-}  // namespace
-
-int rogtk_umi_cluster_host(const void* offsets, int offset_width, const uint8_t* values,
-                           int64_t values_len, const uint8_t* validity, int64_t validity_offset,
-                           int64_t n, int umi_len, int max_distance, uint32_t* cluster_id,
-                           int64_t* n_clusters, int* resolved_umi_len) {
-    HostCol h{offsets, offset_width, values, values_len, validity, validity_offset, n};
-    if (int rc = check_host_col(h)) return rc;
-    ROGTK_REQUIRE(cluster_id || n == 0, ROGTK_E_INVALID, "cluster_id is NULL");
-    ROGTK_REQUIRE(max_distance == 0 || max_distance == 1, ROGTK_E_UNSUPPORTED,
-                  "max_distance %d: only 0 and 1 are supported", max_distance);
-    int L = umi_len > 0 ? umi_len : h.first_len();
-    if (resolved_umi_len) *resolved_umi_len = L;
-    if (n_clusters) *n_clusters = 0;
-    if (n == 0) return ROGTK_OK;
-    HostCtx* c;
-    if (int rc = host_ctx(&c)) return rc;
-    int64_t n_irr = 0;
-    if (int rc = upload_and_stage(c, h, L, &L, &n_irr)) return rc;
-    if (int rc = c->out[0].ensure((size_t)std::max<int64_t>(n, 4) * 4)) return rc;
-    uint32_t* did = c->out[0].as<uint32_t>();
-    int64_t max_len = 0;  // irregular rows and the long engine need it
-    if (n_irr || (L > kMaxPackedLen && L <= 32))
-        if (int rc = device_max_len(c, offset_width, n, &max_len)) return rc;
-    if (int rc = cluster_staged(c, c->offsets.p, offset_width, c->values.as<uint8_t>(),
-                                h.validity ? c->validity.as<uint8_t>() : nullptr, h.voff, n, L, n_irr, max_len,
-                                max_distance, did, n_clusters, c->stream))
-        return rc;
-    return c->d2h(cluster_id, did, (size_t)n * 4);
-}
-
-namespace {
-
-// rogtk_umi_cluster_dev on the context's buffers; *max_len = the column's longest row.
-static int cluster_dev(HostCtx* c, const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
-                int umi_len, int max_distance, uint32_t* cluster_id, int64_t* n_clusters, int64_t* max_len,
-                hipStream_t s) {
-    const int64_t words = (n + 63) / 64;
-    if (c->codes.ensure((size_t)std::max<int64_t>(n, 4) * 4) != ROGTK_OK ||
-        c->regbits.ensure((size_t)std::max<int64_t>(words, 1) * 8) != ROGTK_OK ||
-        c->irr.ensure((size_t)std::max<int64_t>(n, 1) * 8) != ROGTK_OK || c->nirr.ensure(16) != ROGTK_OK)
-        return ROGTK_E_HIP;
-    unsigned long long* cnt = c->nirr.as<unsigned long long>();  // [0] irregular rows, [1] the longest row
-    ROGTK_HIP_CHECK(hipMemsetAsync(cnt, 0, 16, s));
-    if (int rc = launch_stage(offsets, 8, values, validity, 0, n, umi_len, c->codes.as<uint32_t>(),
-                              c->regbits.as<uint64_t>(), c->irr.as<int64_t>(), cnt, s))
-        return rc;
-    if (int rc = launch_max_len(offsets, 8, n, cnt + 1, s)) return rc;
-    int64_t hv[2];  // both words in one read-back and one sync
-    ROGTK_HIP_CHECK(hipMemcpyAsync(hv, cnt, 16, hipMemcpyDeviceToHost, s));
-    ROGTK_HIP_CHECK(hipStreamSynchronize(s));
-    if (max_len) *max_len = hv[1];
-    return cluster_staged(c, offsets, 8, values, validity, 0, n, umi_len, hv[0], hv[1], max_distance, cluster_id,
-                          n_clusters, s);
-}
-
-}  // namespace
-
-int rogtk_umi_cluster_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
-                          int umi_len, int max_distance, uint32_t* cluster_id, int64_t* n_clusters, void* stream) {
-    ROGTK_REQUIRE(n >= 0 && (n == 0 || (offsets && values && cluster_id)), ROGTK_E_INVALID,
-                  "umi_cluster_dev: NULL argument");
-    ROGTK_REQUIRE(umi_len >= 1, ROGTK_E_INVALID, "umi_cluster_dev: umi_len must be >= 1");
-    ROGTK_REQUIRE(max_distance == 0 || max_distance == 1, ROGTK_E_UNSUPPORTED,
-                  "max_distance %d: only 0 and 1 are supported", max_distance);
-    if (n_clusters) *n_clusters = 0;
-    if (n == 0) return ROGTK_OK;
-    HostCtx* c;
-    if (int rc = host_ctx(&c)) return rc;
-    return cluster_dev(c, offsets, values, validity, n, umi_len, max_distance, cluster_id, n_clusters, nullptr,
-                       as_stream(stream));
-}
-
-// ------------------------------------------------- UMI correction (correct.hip)
-int rogtk_cluster_summary_set_method(int method) { return cluster_summary_set_method(method); }
-
-int rogtk_cluster_summary_temp_bytes(int64_t n, int umi_len, int64_t n_clusters, int64_t* bytes) {
-    ROGTK_REQUIRE(bytes, ROGTK_E_INVALID, "cluster_summary_temp_bytes: NULL bytes");
-    ROGTK_REQUIRE(umi_len >= 1 && umi_len <= kMaxPackedLen, ROGTK_E_UNSUPPORTED,
-                  "packed cluster summary: umi_len %d outside 1..%d", umi_len, kMaxPackedLen);
-    if (int rc = check_rows_and_clusters("packed cluster summary", n, n_clusters)) return rc;
-    return cluster_summary_packed_temp(n, umi_len, n_clusters, bytes);
-}
-
-int rogtk_cluster_summary_packed(const uint32_t* codes, const uint64_t* regular_bits, int64_t n, int umi_len,
-                                 const uint32_t* cluster_id, int64_t n_clusters, uint32_t* rep_code, uint32_t* n_reads,
-                                 uint32_t* n_distinct, void* temp, int64_t temp_bytes, void* stream) {
-    ROGTK_REQUIRE(umi_len >= 1 && umi_len <= kMaxPackedLen, ROGTK_E_UNSUPPORTED,
-                  "packed cluster summary: umi_len %d outside 1..%d", umi_len, kMaxPackedLen);
-    if (int rc = check_rows_and_clusters("packed cluster summary", n, n_clusters)) return rc;
-    ROGTK_REQUIRE(n == 0 || (codes && cluster_id), ROGTK_E_INVALID, "packed cluster summary: NULL codes / cluster_id");
-    ROGTK_REQUIRE(n_clusters == 0 || (rep_code && n_reads && n_distinct), ROGTK_E_INVALID,
-                  "packed cluster summary: NULL output table");
-    ROGTK_REQUIRE(temp, ROGTK_E_INVALID, "packed cluster summary: NULL temp");
-    return launch_cluster_summary_packed(codes, regular_bits, n, umi_len, cluster_id, n_clusters, rep_code, n_reads,
-                                         n_distinct, temp, temp_bytes, as_stream(stream));
-}
-
-int rogtk_cluster_correct_packed(const uint32_t* cluster_id, const uint64_t* regular_bits, int64_t n,
-                                 const uint32_t* rep_code, int64_t n_clusters, uint32_t* corrected_codes,
-                                 void* stream) {
-    ROGTK_REQUIRE(n >= 0 && n_clusters >= 0, ROGTK_E_INVALID, "packed correct: negative size");
-    ROGTK_REQUIRE(n == 0 || (cluster_id && corrected_codes && (rep_code || n_clusters == 0)), ROGTK_E_INVALID,
-                  "packed correct: NULL argument");
-    return launch_cluster_correct_packed(cluster_id, regular_bits, n, rep_code, n_clusters, corrected_codes,
-                                         as_stream(stream));
-}
-
-namespace {
-
-static void u32_result_reset(rogtk_u32_result* r) {
-    if (r) *r = rogtk_u32_result{0, nullptr};
-}
-
-static int empty_str_result(int64_t n, rogtk_str_result* out) {
-    const int64_t words = std::max<int64_t>((n + 63) / 64, 1);
-    out->n = n;
-    out->offsets = (int64_t*)calloc((size_t)n + 1, 8);
-    out->values = (uint8_t*)calloc(1, 1);
-    out->validity = (uint8_t*)calloc((size_t)words, 8);
-    out->values_len = 0;
-    out->null_count = 0;
-    ROGTK_REQUIRE(out->offsets && out->values && out->validity, ROGTK_E_INVALID, "out of host memory");
-    return ROGTK_OK;
-}
-
-// The three per-cluster tables of a column on the context's device buffers (ids in did):
-// counts to the host results, representatives measured, filled and copied into `reps`.
-static int summary_to_host(HostCtx* c, const void* d_offsets, int ow, const uint8_t* d_values, const uint8_t* d_validity,
-                    int64_t voff, int64_t n, int L, const uint32_t* did, int64_t nclu, int64_t max_len,
-                    rogtk_str_result* reps, rogtk_u32_result* n_reads, rogtk_u32_result* n_distinct) {
-    hipStream_t s = c->stream;
-    const int64_t nc1 = std::max<int64_t>(nclu, 1);
-    int64_t tb = 0;
-    if (int rc = representatives_temp(nclu, &tb)) return rc;
-    if (c->out[1].ensure((size_t)nc1 * 4) || c->out[2].ensure((size_t)nc1 * 4) || c->out[3].ensure((size_t)nc1 * 8) ||
-        c->out[4].ensure((size_t)(nclu + 1) * 8) || c->out[5].ensure((size_t)tb))
-        return ROGTK_E_HIP;
-    int64_t* rep_row = c->out[3].as<int64_t>();
-    if (int rc = cluster_summary_general(d_offsets, ow, d_values, d_validity, voff, n, L, did, nclu, max_len,
-                                         c->out[1].as<uint32_t>(), c->out[2].as<uint32_t>(), rep_row, s))
-        return rc;
-    if (int rc = representatives_measure(d_offsets, ow, rep_row, nclu, c->out[4].as<int64_t>(), c->out[5].p, tb, s))
-        return rc;
-    if (int rc = empty_str_result(nclu, reps)) return rc;
-    for (rogtk_u32_result* r : {n_reads, n_distinct}) {
-        r->n = nclu;
-        r->data = (uint32_t*)calloc((size_t)nc1, 4);
-        ROGTK_REQUIRE(r->data, ROGTK_E_INVALID, "out of host memory");
-    }
-    if (nclu > 0) {
-        if (int rc = c->d2h(n_reads->data, c->out[1].p, (size_t)nclu * 4)) return rc;
-        if (int rc = c->d2h(n_distinct->data, c->out[2].p, (size_t)nclu * 4)) return rc;
-    }
-    if (int rc = c->d2h(reps->offsets, c->out[4].p, (size_t)(nclu + 1) * 8)) return rc;
-    const int64_t total = reps->offsets[nclu];
-    for (int64_t k = 0; k < nclu; ++k) reps->validity[k >> 3] |= (uint8_t)(1u << (k & 7));
-    if (total > 0) {
-        free(reps->values);
-        reps->values = (uint8_t*)malloc((size_t)total);
-        ROGTK_REQUIRE(reps->values, ROGTK_E_INVALID, "out of host memory for %lld output bytes", (long long)total);
-        reps->values_len = total;
-        if (c->out[6].ensure((size_t)total)) return ROGTK_E_HIP;
-        if (int rc = representatives_fill(d_offsets, ow, d_values, rep_row, nclu, c->out[4].as<int64_t>(),
-                                          c->out[6].as<uint8_t>(), s))
-            return rc;
-        if (int rc = c->d2h(reps->values, c->out[6].p, (size_t)total)) return rc;
-    }
-    return ROGTK_OK;
-}
-
-static int check_correct_outputs(const rogtk_str_col* col, rogtk_str_result* reps, rogtk_u32_result* n_reads,
-                          rogtk_u32_result* n_distinct) {
-    ROGTK_REQUIRE(col, ROGTK_E_INVALID, "NULL column");
-    ROGTK_REQUIRE(reps && n_reads && n_distinct, ROGTK_E_INVALID,
-                  "NULL output (representatives, n_reads and n_distinct are required)");
-    *reps = rogtk_str_result{};
-    u32_result_reset(n_reads);
-    u32_result_reset(n_distinct);
-    return ROGTK_OK;
-}
-
-}  // namespace
-
-int rogtk_cluster_summary_host(const rogtk_str_col* col, int umi_len, const uint32_t* cluster_id, int64_t n_clusters,
-                               rogtk_str_result* representatives, rogtk_u32_result* n_reads,
-                               rogtk_u32_result* n_distinct) {
-    if (int rc = check_correct_outputs(col, representatives, n_reads, n_distinct)) return rc;
-    HostCol h{col->offsets, col->offset_width, col->values, col->values_len, col->validity, col->validity_offset,
-              col->n};
-    if (int rc = check_host_col(h)) return rc;
-    const int64_t n = h.n;
-    ROGTK_REQUIRE(n < (1ll << 31), ROGTK_E_UNSUPPORTED, "cluster summary: at most 2^31 - 1 rows");
-    ROGTK_REQUIRE(cluster_id || n == 0, ROGTK_E_INVALID, "cluster_id is NULL");
-    ROGTK_REQUIRE(n_clusters >= 0 && n_clusters < (1ll << 32) - 1, ROGTK_E_INVALID, "bad n_clusters %lld",
-                  (long long)n_clusters);
-    for (int64_t i = 0; i < n; ++i)
-        ROGTK_REQUIRE(!h.valid(i) || (int64_t)cluster_id[i] < n_clusters, ROGTK_E_INVALID,
-                      "cluster_id[%lld] = %u is >= n_clusters (%lld)", (long long)i, cluster_id[i],
-                      (long long)n_clusters);
-    const int L = umi_len > 0 ? umi_len : h.first_len();
-    HostCtx* c;
-    if (int rc = host_ctx(&c)) return rc;
-    int64_t max_len = 0;
-    if (n > 0) {
-        int Ls = 0;
-        if (int rc = upload_and_stage(c, h, L, &Ls, nullptr)) return rc;
-        if (int rc = device_max_len(c, h.ow, n, &max_len)) return rc;
-    }
-    if (int rc = c->out[0].ensure((size_t)std::max<int64_t>(n, 4) * 4)) return rc;
-    if (n > 0)
-        if (int rc = c->h2d(c->out[0].p, cluster_id, (size_t)n * 4)) return rc;
-    int rc = summary_to_host(c, c->offsets.p, h.ow, c->values.as<uint8_t>(),
-                             h.validity ? c->validity.as<uint8_t>() : nullptr, h.voff, n, L, c->out[0].as<uint32_t>(),
-                             n_clusters, max_len, representatives, n_reads, n_distinct);
-    if (rc) {
-        rogtk_str_result_free(representatives);
-        rogtk_u32_result_free(n_reads);
-        rogtk_u32_result_free(n_distinct);
-    }
-    return rc;
-}
-
-namespace {
-thread_local int64_t t_directional_rounds = 0;  // rogtk_directional_last_rounds
-
-// the argument rules of the grouped entries (include/rogtk_hip.h), before any device work
-static int check_grouped(const char* name, int method, int max_distance) {
-    ROGTK_REQUIRE(method == 0 || method == 1, ROGTK_E_INVALID, "%s: method %d is neither 0 (cluster) nor 1 (directional)",
-                  name, method);
-    ROGTK_REQUIRE(max_distance == 0 || max_distance == 1, ROGTK_E_UNSUPPORTED,
-                  "max_distance %d: only 0 and 1 are supported", max_distance);
-    ROGTK_REQUIRE(method == 1 || max_distance == 0, ROGTK_E_UNSUPPORTED,
-                  "%s: method=\"cluster\" with max_distance 1 is not supported within groups (irregular strings "
-                  "bridge clusters under the transitive rule); use method=\"directional\"",
-                  name);
-    return ROGTK_OK;
-}
-
-// the keys of a host column on the device (c->grp[0]) and room for the clusters' keys (c->grp[1])
-static int upload_groups(HostCtx* c, const uint32_t* groups, int64_t n) {
-    const size_t b = (size_t)std::max<int64_t>(n, 1) * 4;
-    if (int rc = c->grp[0].ensure(b)) return rc;
-    if (int rc = c->grp[1].ensure(b)) return rc;
-    return c->h2d(c->grp[0].p, groups, (size_t)n * 4);
-}
-
-static int groups_to_host(HostCtx* c, int64_t nclu, rogtk_u32_result* cluster_group) {
-    if (!cluster_group) return ROGTK_OK;
-    cluster_group->n = nclu;
-    cluster_group->data = (uint32_t*)calloc((size_t)std::max<int64_t>(nclu, 1), 4);
-    ROGTK_REQUIRE(cluster_group->data, ROGTK_E_INVALID, "out of host memory");
-    return c->d2h(cluster_group->data, c->grp[1].p, (size_t)nclu * 4);
-}
-
-// rogtk_umi_correct_host (directional = false) and rogtk_umi_correct_directional_host at
-// max_distance 1 (directional = true): they differ in the ids alone. groups (nullable): the
-// grouped ids (rogtk_umi_correct_grouped_host) and the clusters' keys into cluster_group.
-static int correct_host(const rogtk_str_col* col, int umi_len, int max_distance, bool directional, uint32_t* cluster_id,
-                        rogtk_str_result* corrected, rogtk_str_result* representatives, rogtk_u32_result* n_reads,
-                        rogtk_u32_result* n_distinct, int64_t* n_clusters, int* resolved_umi_len,
-                        const uint32_t* groups = nullptr, rogtk_u32_result* cluster_group = nullptr) {
-    if (int rc = check_correct_outputs(col, representatives, n_reads, n_distinct)) return rc;
-    u32_result_reset(cluster_group);
-    ROGTK_REQUIRE(corrected, ROGTK_E_INVALID, "NULL output (corrected is required)");
-    *corrected = rogtk_str_result{};
-    HostCol h{col->offsets, col->offset_width, col->values, col->values_len, col->validity, col->validity_offset,
-              col->n};
-    if (int rc = check_host_col(h)) return rc;
-    const int64_t n = h.n;
-    ROGTK_REQUIRE(n < (1ll << 31), ROGTK_E_UNSUPPORTED, "umi_correct: at most 2^31 - 1 rows");
-    ROGTK_REQUIRE(cluster_id || n == 0, ROGTK_E_INVALID, "cluster_id is NULL");
-    ROGTK_REQUIRE(max_distance == 0 || max_distance == 1, ROGTK_E_UNSUPPORTED,
-                  "max_distance %d: only 0 and 1 are supported", max_distance);
-    int L = umi_len > 0 ? umi_len : h.first_len();
-    if (resolved_umi_len) *resolved_umi_len = L;
-    if (n_clusters) *n_clusters = 0;
-    HostCtx* c;
-    if (int rc = host_ctx(&c)) return rc;
-    auto run = [&]() -> int {
-        int64_t nclu = 0, max_len = 0;
-        if (int rc = c->out[0].ensure((size_t)std::max<int64_t>(n, 4) * 4)) return rc;
-        uint32_t* did = c->out[0].as<uint32_t>();
-        const uint8_t* dvalid = h.validity ? c->validity.as<uint8_t>() : nullptr;
-        if (n > 0) {
-            int64_t n_irr = 0;
-            if (int rc = upload_and_stage(c, h, L, &L, &n_irr)) return rc;
-            if (int rc = device_max_len(c, h.ow, n, &max_len)) return rc;
-            dvalid = h.validity ? c->validity.as<uint8_t>() : nullptr;
-            if (groups) {
-                if (int rc = upload_groups(c, groups, n)) return rc;
-                if (int rc = grouped_cluster(c->offsets.p, h.ow, c->values.as<uint8_t>(), dvalid, h.voff, n, L,
-                                             c->grp[0].as<uint32_t>(), max_distance, did, nullptr,
-                                             c->grp[1].as<uint32_t>(), &nclu, &t_directional_rounds, nullptr,
-                                             c->stream))
-                    return rc;
-            } else if (directional) {
-                if (int rc = directional_cluster(c->offsets.p, h.ow, c->values.as<uint8_t>(), dvalid, h.voff, n, L,
-                                                 did, nullptr, &nclu, &t_directional_rounds, nullptr, c->stream))
-                    return rc;
-            } else if (int rc = cluster_staged(c, c->offsets.p, h.ow, c->values.as<uint8_t>(), dvalid, h.voff, n, L,
-                                               n_irr, max_len, max_distance, did, &nclu, c->stream)) {
-                return rc;
-            }
-            if (int rc = c->d2h(cluster_id, did, (size_t)n * 4)) return rc;
-        }
-        if (n_clusters) *n_clusters = nclu;
-        if (groups)
-            if (int rc = groups_to_host(c, nclu, cluster_group)) return rc;
-        if (int rc = summary_to_host(c, c->offsets.p, h.ow, c->values.as<uint8_t>(), dvalid, h.voff, n, L, did, nclu,
-                                     max_len, representatives, n_reads, n_distinct))
-            return rc;
-        // corrected: the input's offsets and nulls, every row's bytes from its representative
-        if (int rc = empty_str_result(n, corrected)) return rc;
-        for (int64_t i = 0; i <= n; ++i) corrected->offsets[i] = h.off(i);
-        for (int64_t i = 0; i < n; ++i) {
-            if (h.valid(i)) corrected->validity[i >> 3] |= (uint8_t)(1u << (i & 7));
-            else ++corrected->null_count;
-        }
-        const int64_t total = n > 0 ? h.off(n) : 0;
-        if (total > 0) {
-            free(corrected->values);
-            corrected->values = (uint8_t*)malloc((size_t)total);
-            ROGTK_REQUIRE(corrected->values, ROGTK_E_INVALID, "out of host memory for %lld output bytes",
-                          (long long)total);
-            corrected->values_len = total;
-            if (c->out[6].ensure((size_t)total)) return ROGTK_E_HIP;
-            ROGTK_HIP_CHECK(hipMemsetAsync(c->out[6].p, 0, (size_t)total, c->stream));
-            if (int rc = corrected_fill(c->offsets.p, h.ow, c->values.as<uint8_t>(), dvalid, h.voff, n, did, nclu,
-                                        c->out[3].as<int64_t>(), c->out[6].as<uint8_t>(), c->stream))
-                return rc;
-            if (int rc = c->d2h(corrected->values, c->out[6].p, (size_t)total)) return rc;
-        }
-        return ROGTK_OK;
-    };
-    const int rc = run();
-    if (rc) {
-        rogtk_str_result_free(corrected);
-        rogtk_str_result_free(representatives);
-        rogtk_u32_result_free(n_reads);
-        rogtk_u32_result_free(n_distinct);
-        rogtk_u32_result_free(cluster_group);
-    }
-    return rc;
-}
-
-}  // namespace
-
-int rogtk_umi_correct_host(const rogtk_str_col* col, int umi_len, int max_distance, uint32_t* cluster_id,
-                           rogtk_str_result* corrected, rogtk_str_result* representatives, rogtk_u32_result* n_reads,
-                           rogtk_u32_result* n_distinct, int64_t* n_clusters, int* resolved_umi_len) {
-    return correct_host(col, umi_len, max_distance, false, cluster_id, corrected, representatives, n_reads, n_distinct,
-                        n_clusters, resolved_umi_len);
-}
-
-void rogtk_u32_result_free(rogtk_u32_result* r) {
-    if (!r) return;
-    free(r->data);
-    *r = rogtk_u32_result{0, nullptr};
-}
-
-int rogtk_cluster_summary_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
-                              int umi_len, const uint32_t* cluster_id, int64_t n_clusters, uint32_t* n_reads,
-                              uint32_t* n_distinct, int64_t* rep_rows, int64_t* rep_offsets, int64_t* rep_values_len,
-                              void* stream) {
-    if (int rc = check_rows_and_clusters("cluster_summary_dev", n, n_clusters)) return rc;
-    ROGTK_REQUIRE(n == 0 || (offsets && values && cluster_id), ROGTK_E_INVALID, "cluster_summary_dev: NULL input");
-    ROGTK_REQUIRE(n_reads && n_distinct && rep_rows && rep_offsets && rep_values_len, ROGTK_E_INVALID,
-                  "cluster_summary_dev: NULL output");
-    ROGTK_REQUIRE(umi_len >= 1, ROGTK_E_INVALID, "cluster_summary_dev: umi_len must be >= 1");
-    *rep_values_len = 0;
-    hipStream_t s = as_stream(stream);
-    HostCtx* c;
-    if (int rc = host_ctx(&c)) return rc;
-    int64_t max_len = 0;
-    if (n > 0) {
-        if (int rc = c->nirr.ensure(16)) return rc;
-        if (int rc = column_max_len(offsets, 8, n, c->nirr.as<unsigned long long>() + 1, s, &max_len)) return rc;
-    }
-    if (int rc = cluster_summary_general(offsets, 8, values, validity, 0, n, umi_len, cluster_id, n_clusters, max_len,
-                                         n_reads, n_distinct, rep_rows, s))
-        return rc;
-    int64_t tb = 0;
-    if (int rc = representatives_temp(n_clusters, &tb)) return rc;
-    if (int rc = c->out[5].ensure((size_t)tb)) return rc;
-    if (int rc = representatives_measure(offsets, 8, rep_rows, n_clusters, rep_offsets, c->out[5].p, tb, s)) return rc;
-    ROGTK_HIP_CHECK(hipMemcpyAsync(rep_values_len, rep_offsets + n_clusters, 8, hipMemcpyDeviceToHost, s));
-    ROGTK_HIP_CHECK(hipStreamSynchronize(s));
-    return ROGTK_OK;
-}
-
-int rogtk_cluster_representatives_fill(const int64_t* offsets, const uint8_t* values, const int64_t* rep_rows,
-                                       int64_t n_clusters, const int64_t* rep_offsets, uint8_t* rep_values,
-                                       void* stream) {
-    ROGTK_REQUIRE(n_clusters >= 0, ROGTK_E_INVALID, "representatives_fill: negative n_clusters");
-    ROGTK_REQUIRE(n_clusters == 0 || (offsets && values && rep_rows && rep_offsets && rep_values), ROGTK_E_INVALID,
-                  "representatives_fill: NULL argument");
-    return representatives_fill(offsets, 8, values, rep_rows, n_clusters, rep_offsets, rep_values, as_stream(stream));
-}
-
-namespace {
-// the tail of both *_correct*_dev entries: the per-cluster summary on the context's buffers,
-// then every row's bytes from its cluster's representative
-int correct_tail_dev(HostCtx* c, const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
-                     int umi_len, const uint32_t* cluster_id, int64_t nclu, int64_t max_len, uint8_t* corrected_values,
-                     hipStream_t s) {
-    const int64_t nc1 = std::max<int64_t>(nclu, 1);
-    if (c->out[1].ensure((size_t)nc1 * 4) || c->out[2].ensure((size_t)nc1 * 4) || c->out[3].ensure((size_t)nc1 * 8))
-        return ROGTK_E_HIP;
-    int64_t* rep_row = c->out[3].as<int64_t>();
-    if (int rc = cluster_summary_general(offsets, 8, values, validity, 0, n, umi_len, cluster_id, nclu, max_len,
-                                         c->out[1].as<uint32_t>(), c->out[2].as<uint32_t>(), rep_row, s))
-        return rc;
-    return corrected_fill(offsets, 8, values, validity, 0, n, cluster_id, nclu, rep_row, corrected_values, s);
-}
-}  // namespace
-
-int rogtk_umi_correct_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
-                          int umi_len, int max_distance, uint32_t* cluster_id, int64_t* n_clusters,
-                          uint8_t* corrected_values, void* stream) {
-    if (int rc = check_rows_and_clusters("umi_correct_dev", n, 0)) return rc;
-    ROGTK_REQUIRE(n == 0 || (offsets && values && cluster_id && corrected_values), ROGTK_E_INVALID,
-                  "umi_correct_dev: NULL argument");
-    ROGTK_REQUIRE(umi_len >= 1, ROGTK_E_INVALID, "umi_correct_dev: umi_len must be >= 1");
-    ROGTK_REQUIRE(max_distance == 0 || max_distance == 1, ROGTK_E_UNSUPPORTED,
-                  "max_distance %d: only 0 and 1 are supported", max_distance);
-    if (n_clusters) *n_clusters = 0;
-    if (n == 0) return ROGTK_OK;
-    hipStream_t s = as_stream(stream);
-    HostCtx* c;
-    if (int rc = host_ctx(&c)) return rc;
-    int64_t nclu = 0, max_len = 0;
-    if (int rc = cluster_dev(c, offsets, values, validity, n, umi_len, max_distance, cluster_id, &nclu, &max_len, s))
-        return rc;
-    if (n_clusters) *n_clusters = nclu;
-    return correct_tail_dev(c, offsets, values, validity, n, umi_len, cluster_id, nclu, max_len, corrected_values, s);
-}
-
-// ------------------------------------ directional UMI clustering (directional.hip)
-int rogtk_directional_temp_bytes(int64_t m, int umi_len, int64_t* bytes) {
-    ROGTK_REQUIRE(bytes, ROGTK_E_INVALID, "directional_temp_bytes: NULL bytes");
-    ROGTK_REQUIRE(umi_len >= 1 && umi_len <= 32, ROGTK_E_UNSUPPORTED, "directional: umi_len %d outside 1..32", umi_len);
-    ROGTK_REQUIRE(m >= 0 && m < (1ll << 31), ROGTK_E_UNSUPPORTED, "directional: m %lld outside 0..2^31-1",
-                  (long long)m);
-    return directional_codes_temp(m, umi_len, bytes);
-}
-
-int rogtk_directional_codes(const uint64_t* codes, const uint32_t* counts, int64_t m, int umi_len, uint32_t* root,
-                            uint32_t* labels, int64_t* n_clusters, int64_t* rounds, void* temp, int64_t temp_bytes,
-                            void* stream) {
-    ROGTK_REQUIRE(umi_len >= 1 && umi_len <= 32, ROGTK_E_UNSUPPORTED, "directional: umi_len %d outside 1..32", umi_len);
-    ROGTK_REQUIRE(m >= 0 && m < (1ll << 31), ROGTK_E_UNSUPPORTED, "directional: m %lld outside 0..2^31-1",
-                  (long long)m);
-    ROGTK_REQUIRE(n_clusters && rounds, ROGTK_E_INVALID, "directional: NULL n_clusters / rounds");
-    ROGTK_REQUIRE(m == 0 || (codes && counts && root && labels && temp), ROGTK_E_INVALID, "directional: NULL argument");
-    const int rc = directional_codes(codes, counts, m, umi_len, root, labels, n_clusters, rounds, temp, temp_bytes,
-                                     as_stream(stream));
-    t_directional_rounds = *rounds;
-    return rc;
-}
-
-int rogtk_directional_last_rounds(int64_t* rounds) {
-    ROGTK_REQUIRE(rounds, ROGTK_E_INVALID, "directional_last_rounds: NULL rounds");
-    *rounds = t_directional_rounds;
-    return ROGTK_OK;
-}
-
-int rogtk_umi_cluster_directional_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
-                                      int umi_len, uint32_t* cluster_id, int64_t* n_clusters, uint64_t* root_code,
-                                      void* stream) {
-    if (int rc = check_rows_and_clusters("umi_cluster_directional_dev", n, 0)) return rc;
-    ROGTK_REQUIRE(n == 0 || (offsets && values && cluster_id), ROGTK_E_INVALID,
-                  "umi_cluster_directional_dev: NULL argument");
-    ROGTK_REQUIRE(umi_len >= 1, ROGTK_E_INVALID, "umi_cluster_directional_dev: umi_len must be >= 1");
-    int64_t nclu = 0;
-    t_directional_rounds = 0;
-    if (n_clusters) *n_clusters = 0;
-    if (n == 0) return ROGTK_OK;
-    if (int rc = directional_cluster(offsets, 8, values, validity, 0, n, umi_len, cluster_id, root_code, &nclu,
-                                     &t_directional_rounds, nullptr, as_stream(stream)))
-        return rc;
-    if (n_clusters) *n_clusters = nclu;
-    return ROGTK_OK;
-}
-
-int rogtk_umi_correct_directional_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
-                                      int umi_len, uint32_t* cluster_id, int64_t* n_clusters,
-                                      uint8_t* corrected_values, void* stream) {
-    if (int rc = check_rows_and_clusters("umi_correct_directional_dev", n, 0)) return rc;
-    ROGTK_REQUIRE(n == 0 || (offsets && values && cluster_id && corrected_values), ROGTK_E_INVALID,
-                  "umi_correct_directional_dev: NULL argument");
-    ROGTK_REQUIRE(umi_len >= 1, ROGTK_E_INVALID, "umi_correct_directional_dev: umi_len must be >= 1");
-    if (n_clusters) *n_clusters = 0;
-    t_directional_rounds = 0;
-    if (n == 0) return ROGTK_OK;
-    hipStream_t s = as_stream(stream);
-    HostCtx* c;
-    if (int rc = host_ctx(&c)) return rc;
-    int64_t nclu = 0, max_len = 0;
-    if (int rc = directional_cluster(offsets, 8, values, validity, 0, n, umi_len, cluster_id, nullptr, &nclu,
-                                     &t_directional_rounds, &max_len, s))
-        return rc;
-    if (n_clusters) *n_clusters = nclu;
-    return correct_tail_dev(c, offsets, values, validity, n, umi_len, cluster_id, nclu, max_len, corrected_values, s);
-}
-
-int rogtk_umi_cluster_directional_host(const void* offsets, int offset_width, const uint8_t* values, int64_t values_len,
-                                       const uint8_t* validity, int64_t validity_offset, int64_t n, int umi_len,
-                                       int max_distance, uint32_t* cluster_id, int64_t* n_clusters,
-                                       int* resolved_umi_len) {
-    ROGTK_REQUIRE(max_distance == 0 || max_distance == 1, ROGTK_E_UNSUPPORTED,
-                  "max_distance %d: only 0 and 1 are supported", max_distance);
-    if (max_distance == 0)  // no edges: the exact grouping, one implementation
-        return rogtk_umi_cluster_host(offsets, offset_width, values, values_len, validity, validity_offset, n, umi_len,
-                                      0, cluster_id, n_clusters, resolved_umi_len);
-    HostCol h{offsets, offset_width, values, values_len, validity, validity_offset, n};
-    if (int rc = check_host_col(h)) return rc;
-    ROGTK_REQUIRE(n < (1ll << 31), ROGTK_E_UNSUPPORTED, "umi_cluster_directional: at most 2^31 - 1 rows");
-    ROGTK_REQUIRE(cluster_id || n == 0, ROGTK_E_INVALID, "cluster_id is NULL");
-    int L = umi_len > 0 ? umi_len : h.first_len();
-    if (resolved_umi_len) *resolved_umi_len = L;
-    if (n_clusters) *n_clusters = 0;
-    t_directional_rounds = 0;
-    if (n == 0) return ROGTK_OK;
-    HostCtx* c;
-    if (int rc = host_ctx(&c)) return rc;
-    if (int rc = upload_and_stage(c, h, L, &L, nullptr)) return rc;
-    if (int rc = c->out[0].ensure((size_t)std::max<int64_t>(n, 4) * 4)) return rc;
-    uint32_t* did = c->out[0].as<uint32_t>();
-    int64_t nclu = 0;
-    if (int rc = directional_cluster(c->offsets.p, offset_width, c->values.as<uint8_t>(),
-                                     h.validity ? c->validity.as<uint8_t>() : nullptr, h.voff, n, L, did, nullptr,
-                                     &nclu, &t_directional_rounds, nullptr, c->stream))
-        return rc;
-    if (n_clusters) *n_clusters = nclu;
-    return c->d2h(cluster_id, did, (size_t)n * 4);
-}
-
-int rogtk_umi_correct_directional_host(const rogtk_str_col* col, int umi_len, int max_distance, uint32_t* cluster_id,
-                                       rogtk_str_result* corrected, rogtk_str_result* representatives,
-                                       rogtk_u32_result* n_reads, rogtk_u32_result* n_distinct, int64_t* n_clusters,
-                                       int* resolved_umi_len) {
-    return correct_host(col, umi_len, max_distance, max_distance == 1, cluster_id, corrected, representatives, n_reads,
-                        n_distinct, n_clusters, resolved_umi_len);
-}
-
-// ------------------------------------ clustering within groups (grouped.hip)
-int rogtk_grouped_set_window(int window) { return grouped_set_window(window); }
-
-int rogtk_umi_cluster_grouped_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
-                                  const uint32_t* groups, int umi_len, int method, int max_distance,
-                                  uint32_t* cluster_id, int64_t* n_clusters, uint64_t* root_code,
-                                  uint32_t* cluster_group, void* stream) {
-    if (int rc = check_rows_and_clusters("umi_cluster_grouped_dev", n, 0)) return rc;
-    if (int rc = check_grouped("umi_cluster_grouped_dev", method, max_distance)) return rc;
-    ROGTK_REQUIRE(n == 0 || (offsets && values && cluster_id && groups), ROGTK_E_INVALID,
-                  "umi_cluster_grouped_dev: NULL argument");
-    ROGTK_REQUIRE(umi_len >= 1, ROGTK_E_INVALID, "umi_cluster_grouped_dev: umi_len must be >= 1");
-    int64_t nclu = 0;
-    t_directional_rounds = 0;
-    if (n_clusters) *n_clusters = 0;
-    if (n == 0) return ROGTK_OK;
-    if (int rc = grouped_cluster(offsets, 8, values, validity, 0, n, umi_len, groups, max_distance, cluster_id,
-                                 root_code, cluster_group, &nclu, &t_directional_rounds, nullptr, as_stream(stream)))
-        return rc;
-    if (n_clusters) *n_clusters = nclu;
-    return ROGTK_OK;
-}
-
-int rogtk_umi_correct_grouped_dev(const int64_t* offsets, const uint8_t* values, const uint8_t* validity, int64_t n,
-                                  const uint32_t* groups, int umi_len, int method, int max_distance,
-                                  uint32_t* cluster_id, int64_t* n_clusters, uint8_t* corrected_values,
-                                  uint32_t* cluster_group, void* stream) {
-    if (int rc = check_rows_and_clusters("umi_correct_grouped_dev", n, 0)) return rc;
-    if (int rc = check_grouped("umi_correct_grouped_dev", method, max_distance)) return rc;
-    ROGTK_REQUIRE(n == 0 || (offsets && values && cluster_id && corrected_values && groups), ROGTK_E_INVALID,
-                  "umi_correct_grouped_dev: NULL argument");
-    ROGTK_REQUIRE(umi_len >= 1, ROGTK_E_INVALID, "umi_correct_grouped_dev: umi_len must be >= 1");
-    if (n_clusters) *n_clusters = 0;
-    t_directional_rounds = 0;
-    if (n == 0) return ROGTK_OK;
-    hipStream_t s = as_stream(stream);
-    HostCtx* c;
-    if (int rc = host_ctx(&c)) return rc;
-    int64_t nclu = 0, max_len = 0;
-    if (int rc = grouped_cluster(offsets, 8, values, validity, 0, n, umi_len, groups, max_distance, cluster_id, nullptr,
-                                 cluster_group, &nclu, &t_directional_rounds, &max_len, s))
-        return rc;
-    if (n_clusters) *n_clusters = nclu;
-    return correct_tail_dev(c, offsets, values, validity, n, umi_len, cluster_id, nclu, max_len, corrected_values, s);
-}
-
-int rogtk_umi_cluster_grouped_host(const void* offsets, int offset_width, const uint8_t* values, int64_t values_len,
-                                   const uint8_t* validity, int64_t validity_offset, int64_t n,
-                                   const uint32_t* groups, int umi_len, int method, int max_distance,
-                                   uint32_t* cluster_id, int64_t* n_clusters, int* resolved_umi_len,
-                                   rogtk_u32_result* cluster_group) {
-    u32_result_reset(cluster_group);
-    if (int rc = check_grouped("umi_cluster_grouped", method, max_distance)) return rc;
-    HostCol h{offsets, offset_width, values, values_len, validity, validity_offset, n};
-    if (int rc = check_host_col(h)) return rc;
-    ROGTK_REQUIRE(n < (1ll << 31), ROGTK_E_UNSUPPORTED, "umi_cluster_grouped: at most 2^31 - 1 rows");
-    ROGTK_REQUIRE((cluster_id && groups) || n == 0, ROGTK_E_INVALID, "cluster_id or groups is NULL");
-    int L = umi_len > 0 ? umi_len : h.first_len();
-    if (resolved_umi_len) *resolved_umi_len = L;
-    if (n_clusters) *n_clusters = 0;
-    t_directional_rounds = 0;
-    if (n == 0) return ROGTK_OK;
-    HostCtx* c;
-    if (int rc = host_ctx(&c)) return rc;
-    if (int rc = upload_and_stage(c, h, L, &L, nullptr)) return rc;
-    if (int rc = c->out[0].ensure((size_t)std::max<int64_t>(n, 4) * 4)) return rc;
-    if (int rc = upload_groups(c, groups, n)) return rc;
-    uint32_t* did = c->out[0].as<uint32_t>();
-    int64_t nclu = 0;
-    if (int rc = grouped_cluster(c->offsets.p, offset_width, c->values.as<uint8_t>(),
-                                 h.validity ? c->validity.as<uint8_t>() : nullptr, h.voff, n, L,
-                                 c->grp[0].as<uint32_t>(), max_distance, did, nullptr, c->grp[1].as<uint32_t>(), &nclu,
-                                 &t_directional_rounds, nullptr, c->stream))
-        return rc;
-    if (n_clusters) *n_clusters = nclu;
-    if (int rc = c->d2h(cluster_id, did, (size_t)n * 4)) return rc;
-    const int rc = groups_to_host(c, nclu, cluster_group);
-    if (rc) rogtk_u32_result_free(cluster_group);
-    return rc;
-}
-
-int rogtk_umi_correct_grouped_host(const rogtk_str_col* col, const uint32_t* groups, int umi_len, int method,
-                                   int max_distance, uint32_t* cluster_id, rogtk_str_result* corrected,
-                                   rogtk_str_result* representatives, rogtk_u32_result* n_reads,
-                                   rogtk_u32_result* n_distinct, rogtk_u32_result* cluster_group,
-                                   int64_t* n_clusters, int* resolved_umi_len) {
-    u32_result_reset(cluster_group);
-    if (int rc = check_grouped("umi_correct_grouped", method, max_distance)) return rc;
-    ROGTK_REQUIRE(groups || !col || col->n == 0, ROGTK_E_INVALID, "umi_correct_grouped: groups is NULL");
-    static const uint32_t no_rows = 0;  // an empty column still takes the grouped path
-    t_directional_rounds = 0;
-    return correct_host(col, umi_len, max_distance, true, cluster_id, corrected, representatives, n_reads, n_distinct,
-                        n_clusters, resolved_umi_len, groups ? groups : &no_rows, cluster_group);
-}
-
 // ------------------------------------ cell-barcode correction (barcode.hip)
 int rogtk_barcode_set_probe(int probe) { return barcode_set_probe(probe); }
 
 int rogtk_barcode_whitelist_create(const rogtk_str_col* wl, void** out) {
     ROGTK_REQUIRE(wl && out, ROGTK_E_INVALID, "barcode whitelist: NULL argument");
     *out = nullptr;
-    HostCol h{wl->offsets, wl->offset_width, wl->values, wl->values_len, wl->validity, wl->validity_offset, wl->n};
+    const HostCol h(*wl);
     if (int rc = check_host_col(h)) return rc;
     const int64_t W = h.n;
     ROGTK_REQUIRE(W >= 1, ROGTK_E_INVALID, "barcode whitelist: empty");
@@ -1787,23 +1038,6 @@ static int check_barcode(const char* name, const void* handle, int64_t n, int am
     return barcode_whitelist_info(handle, W, nullptr, nullptr, nullptr);
 }
 
-// the offsets, values and validity of a host column on the context's buffers (no staging pass)
-static int upload_col(HostCtx* c, const HostCol& h) {
-    const int64_t n = h.n;
-    ROGTK_REQUIRE(h.off(n) <= h.values_len || h.values_len < 0, ROGTK_E_INVALID,
-                  "offsets reference %lld bytes but values_len is %lld", (long long)h.off(n), (long long)h.values_len);
-    if (int rc = c->offsets.ensure((size_t)(n + 1) * h.ow)) return rc;
-    if (int rc = c->h2d(c->offsets.p, h.offsets, (size_t)(n + 1) * h.ow)) return rc;
-    if (int rc = c->values.ensure((size_t)std::max<int64_t>(h.off(n), 1))) return rc;
-    if (int rc = c->h2d(c->values.p, h.values, (size_t)h.off(n))) return rc;
-    if (h.validity) {
-        const size_t vb = (size_t)((h.voff + n + 7) / 8);
-        if (int rc = c->validity.ensure(vb)) return rc;
-        if (int rc = c->h2d(c->validity.p, h.validity, vb)) return rc;
-    }
-    return ROGTK_OK;
-}
-
 }  // namespace
 
 int rogtk_barcode_correct_dev(const void* handle, const int64_t* offsets, const uint8_t* values,
@@ -1816,7 +1050,7 @@ int rogtk_barcode_correct_dev(const void* handle, const int64_t* offsets, const 
                   "barcode_correct_dev: NULL argument");
     static uint32_t no_index;  // an empty column still runs the correcting path
     static uint8_t no_status;
-    return barcode_correct(handle, offsets, 8, values, validity, 0, n, ambiguous, prior_counts,
+    return barcode_correct(handle, DevCol(offsets, values, validity, n), ambiguous, prior_counts,
                            index ? index : &no_index, status ? status : &no_status, exact_counts, counts, false,
                            totals5, as_stream(stream));
 }
@@ -1827,7 +1061,7 @@ int rogtk_barcode_count_dev(const void* handle, const int64_t* offsets, const ui
     int64_t W = 0;
     if (int rc = check_barcode("barcode_count_dev", handle, n, ROGTK_BC_COUNTS, &W)) return rc;
     ROGTK_REQUIRE(exact_counts && (n == 0 || (offsets && values)), ROGTK_E_INVALID, "barcode_count_dev: NULL argument");
-    return barcode_correct(handle, offsets, 8, values, validity, 0, n, ROGTK_BC_COUNTS, nullptr, nullptr, nullptr,
+    return barcode_correct(handle, DevCol(offsets, values, validity, n), ROGTK_BC_COUNTS, nullptr, nullptr, nullptr,
                            exact_counts, nullptr, true, totals5, as_stream(stream));
 }
 
@@ -1835,17 +1069,15 @@ int rogtk_barcode_count_host(const void* handle, const rogtk_str_col* col, uint3
     ROGTK_REQUIRE(col && exact_counts, ROGTK_E_INVALID, "barcode_count: NULL argument");
     int64_t W = 0;
     if (int rc = check_barcode("barcode_count", handle, col->n, ROGTK_BC_COUNTS, &W)) return rc;
-    HostCol h{col->offsets, col->offset_width, col->values, col->values_len, col->validity, col->validity_offset,
-              col->n};
+    const HostCol h(*col);
     if (int rc = check_host_col(h)) return rc;
     HostCtx* c;
     if (int rc = host_ctx(&c)) return rc;
     if (int rc = upload_col(c, h)) return rc;
     if (int rc = c->out[1].ensure((size_t)W * 4)) return rc;
     if (int rc = c->h2d(c->out[1].p, exact_counts, (size_t)W * 4)) return rc;
-    if (int rc = barcode_correct(handle, c->offsets.p, h.ow, c->values.as<uint8_t>(),
-                                 h.validity ? c->validity.as<uint8_t>() : nullptr, h.voff, h.n, ROGTK_BC_COUNTS, nullptr,
-                                 nullptr, nullptr, c->out[1].as<uint32_t>(), nullptr, true, totals5, c->stream))
+    if (int rc = barcode_correct(handle, DevCol(c, h), ROGTK_BC_COUNTS, nullptr, nullptr, nullptr,
+                                 c->out[1].as<uint32_t>(), nullptr, true, totals5, c->stream))
         return rc;
     return c->d2h(exact_counts, c->out[1].p, (size_t)W * 4);
 }
@@ -1858,8 +1090,7 @@ int rogtk_barcode_correct_host(const void* handle, const rogtk_str_col* col, int
     ROGTK_REQUIRE(col, ROGTK_E_INVALID, "barcode_correct: NULL column");
     int64_t W = 0;
     if (int rc = check_barcode("barcode_correct", handle, col->n, ambiguous, &W)) return rc;
-    HostCol h{col->offsets, col->offset_width, col->values, col->values_len, col->validity, col->validity_offset,
-              col->n};
+    const HostCol h(*col);
     if (int rc = check_host_col(h)) return rc;
     const int64_t n = h.n;
     ROGTK_REQUIRE(n == 0 || (index && status), ROGTK_E_INVALID, "barcode_correct: index or status is NULL");
@@ -1875,9 +1106,8 @@ int rogtk_barcode_correct_host(const void* handle, const rogtk_str_col* col, int
         uint8_t* d_status = c->out[7].as<uint8_t>();
         if (prior_counts)
             if (int rc = c->h2d(c->out[3].p, prior_counts, (size_t)W * 4)) return rc;
-        if (int rc = barcode_correct(handle, c->offsets.p, h.ow, c->values.as<uint8_t>(),
-                                     h.validity ? c->validity.as<uint8_t>() : nullptr, h.voff, n, ambiguous,
-                                     prior_counts ? c->out[3].as<uint32_t>() : nullptr, d_index, d_status,
+        if (int rc = barcode_correct(handle, DevCol(c, h), ambiguous, prior_counts ? c->out[3].as<uint32_t>() : nullptr,
+                                     d_index, d_status,
                                      c->out[1].as<uint32_t>(), c->out[2].as<uint32_t>(), false, totals5, c->stream))
             return rc;
         if (n > 0) {

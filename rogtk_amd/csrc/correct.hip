@@ -23,6 +23,7 @@
 #include <atomic>
 
 #include "column_util.h"
+#include "level2.h"
 
 namespace rogtk {
 namespace {
@@ -530,9 +531,9 @@ int launch_cluster_correct_packed(const uint32_t* ids, const uint64_t* regbits, 
     return ROGTK_OK;
 }
 
-int cluster_summary_general(const void* offsets, int ow, const uint8_t* values, const uint8_t* validity, int64_t voff,
-                            int64_t n, int L, const uint32_t* ids, int64_t n_clusters, int64_t max_len,
+int cluster_summary_general(const DevCol& col, int L, const uint32_t* ids, int64_t n_clusters, int64_t max_len,
                             uint32_t* n_reads, uint32_t* n_distinct, int64_t* rep_row, hipStream_t s) {
+    const auto [offsets, ow, values, validity, voff, n] = col;
     ROGTK_REQUIRE(n < (1ll << 31), ROGTK_E_UNSUPPORTED, "cluster summary: at most 2^31 - 1 rows");
     if (ow == 4)
         return summary_general<4>(offsets, values, validity, voff, n, L, ids, n_clusters, max_len, n_reads, n_distinct,
@@ -549,8 +550,10 @@ int representatives_temp(int64_t n_clusters, int64_t* bytes) {
     return ROGTK_OK;
 }
 
-int representatives_measure(const void* offsets, int ow, const int64_t* rep_row, int64_t n_clusters,
-                            int64_t* out_offsets, void* temp, int64_t temp_bytes, hipStream_t s) {
+int representatives_measure(const DevCol& col, const int64_t* rep_row, int64_t n_clusters, int64_t* out_offsets,
+                            void* temp, int64_t temp_bytes, hipStream_t s) {
+    const void* offsets = col.offsets;
+    const int ow = col.ow;
     int64_t need = 0;
     if (int rc = representatives_temp(n_clusters, &need)) return rc;
     ROGTK_REQUIRE(temp && need <= temp_bytes, ROGTK_E_INVALID, "representatives: temp_bytes %lld too small (need %lld)",
@@ -579,9 +582,9 @@ int representatives_fill(const void* offsets, int ow, const uint8_t* values, con
     return ROGTK_OK;
 }
 
-int corrected_fill(const void* offsets, int ow, const uint8_t* values, const uint8_t* validity, int64_t voff,
-                   int64_t n, const uint32_t* ids, int64_t n_clusters, const int64_t* rep_row, uint8_t* out_values,
-                   hipStream_t s) {
+int corrected_fill(const DevCol& col, const uint32_t* ids, int64_t n_clusters, const int64_t* rep_row,
+                   uint8_t* out_values, hipStream_t s) {
+    const auto [offsets, ow, values, validity, voff, n] = col;
     if (n <= 0) return ROGTK_OK;
     const dim3 g(grid_for(n, kBlock)), b(kBlock);
     if (ow == 4)

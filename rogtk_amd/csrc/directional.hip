@@ -28,6 +28,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "column_util.h"
+#include "level2.h"
 #include "directional_rounds.h"
 
 namespace rogtk {
@@ -282,9 +283,9 @@ int directional_codes(const uint64_t* D, const uint32_t* C, int64_t m, int L, ui
     return ROGTK_OK;
 }
 
-int directional_cluster(const void* offsets, int ow, const uint8_t* values, const uint8_t* validity, int64_t voff,
-                        int64_t n, int L, uint32_t* cluster_id, uint64_t* root_code, int64_t* n_clusters,
+int directional_cluster(const DevCol& col, int L, uint32_t* cluster_id, uint64_t* root_code, int64_t* n_clusters,
                         int64_t* rounds, int64_t* longest, hipStream_t s) {
+    const auto [offsets, ow, values, validity, voff, n] = col;
     *n_clusters = 0;
     *rounds = 0;
     if (longest) *longest = 0;
@@ -298,7 +299,7 @@ int directional_cluster(const void* offsets, int ow, const uint8_t* values, cons
         return (int)ROGTK_OK;
     };
     SortedCodes sc;
-    if (int rc = sorted_distinct_codes(offsets, ow, values, validity, voff, n, L, true, &extra, cluster_id, &sc, s))
+    if (int rc = sorted_distinct_codes(col, L, true, &extra, cluster_id, &sc, s))
         return rc;
     if (longest) *longest = std::max<int64_t>(sc.max_irr_len, sc.n_reg > 0 ? L : 0);
     const int64_t m = sc.m;

@@ -24,6 +24,7 @@
 #include <atomic>
 
 #include "column_util.h"
+#include "level2.h"
 
 namespace rogtk {
 namespace {
@@ -82,10 +83,10 @@ int grouped_set_window(int window) {
     return ROGTK_OK;
 }
 
-int grouped_cluster(const void* offsets, int ow, const uint8_t* values, const uint8_t* validity, int64_t voff,
-                    int64_t n, int L, const uint32_t* groups, int max_distance, uint32_t* cluster_id,
+int grouped_cluster(const DevCol& col, int L, const uint32_t* groups, int max_distance, uint32_t* cluster_id,
                     uint64_t* root_code, uint32_t* cluster_group, int64_t* n_clusters, int64_t* rounds,
                     int64_t* longest, hipStream_t s) {
+    const auto [offsets, ow, values, validity, voff, n] = col;
     *n_clusters = 0;
     *rounds = 0;
     if (longest) *longest = 0;
@@ -113,7 +114,7 @@ int grouped_cluster(const void* offsets, int ow, const uint8_t* values, const ui
         return (int)ROGTK_OK;
     };
     SortedCodes sc;
-    if (int rc = sorted_distinct_codes(offsets, ow, values, validity, voff, n, L, true, &extra, cluster_id, &sc, s,
+    if (int rc = sorted_distinct_codes(col, L, true, &extra, cluster_id, &sc, s,
                                        groups))
         return rc;
     if (longest) *longest = std::max<int64_t>(sc.max_irr_len, sc.n_reg > 0 ? L : 0);

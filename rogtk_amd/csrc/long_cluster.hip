@@ -21,6 +21,7 @@
 #include <cstdlib>
 
 #include "column_util.h"
+#include "level2.h"
 
 namespace rogtk {
 namespace {
@@ -75,9 +76,9 @@ int clique_edges(const uint64_t* D, int64_t nd, int L, uint2* E, int64_t* n_edge
 
 }  // namespace
 
-int long_cluster(const void* offsets, int ow, const uint8_t* values, const uint8_t* validity, int64_t voff,
-                 int64_t n, int L, int max_distance, int64_t max_len, uint32_t* cid, int64_t* n_clusters,
+int long_cluster(const DevCol& col, int L, int max_distance, int64_t max_len, uint32_t* cid, int64_t* n_clusters,
                  hipStream_t s) {
+    const auto [offsets, ow, values, validity, voff, n] = col;
     ROGTK_REQUIRE(L > kMaxPackedLen && L <= 32, ROGTK_E_UNSUPPORTED, "long_cluster: umi_len %d outside 17..32", L);
     ROGTK_REQUIRE(n < (1ll << 31), ROGTK_E_UNSUPPORTED, "long_cluster: more than 2^31 rows");
     if (n_clusters) *n_clusters = 0;
@@ -89,7 +90,7 @@ int long_cluster(const void* offsets, int ow, const uint8_t* values, const uint8
         return (int)ROGTK_OK;
     };
     SortedCodes sc;
-    if (int rc = sorted_distinct_codes(offsets, ow, values, validity, voff, n, L, false, &extra, cid, &sc, s))
+    if (int rc = sorted_distinct_codes(col, L, false, &extra, cid, &sc, s))
         return rc;
     const int64_t nd = sc.m;  // distinct regular codes
     int64_t* stats = sc.spare;

@@ -398,19 +398,18 @@ int cc_labels(int64_t nv, const uint32_t* edges, int64_t m, uint32_t* labels, in
 // are added to out->codes_mem for the caller to take, which saves the engine an arena of its
 // own (each one is a real allocation and release; profiles/refactor_sort_engines.json).
 struct SortedCodes;
+struct DevCol;  // a device string column as one value (level2.h)
 using ExtraCodeBytes = std::function<int(int64_t m, size_t* bytes)>;
 // groups (nullable, device, one u32 key per row): D holds the composites
 // key << 2 L | code of the regular rows, sorted over exactly 2 L + bit_width(largest key) bits
 // (out->key_bits; ROGTK_E_UNSUPPORTED past 64, seen after the pack kernel's read-back), and
 // out->max_group / max_irr_group are the largest keys of the regular / irregular rows.
-int sorted_distinct_codes(const void* offsets, int ow, const uint8_t* values, const uint8_t* validity, int64_t voff,
-                          int64_t n, int L, bool want_counts, const ExtraCodeBytes* extra, uint32_t* cluster_id,
+int sorted_distinct_codes(const DevCol& col, int L, bool want_counts, const ExtraCodeBytes* extra, uint32_t* cluster_id,
                           SortedCodes* out, hipStream_t s, const uint32_t* groups = nullptr);
 
 // H3 for 17 <= L <= 32 (sort-based, long_cluster.hip): regular + irregular rows of a
 // device column; ids into cid (device), *n_clusters on the host. Synchronises s.
-int long_cluster(const void* offsets, int ow, const uint8_t* values, const uint8_t* validity, int64_t voff,
-                 int64_t n, int L, int max_distance, int64_t max_len, uint32_t* cid, int64_t* n_clusters,
+int long_cluster(const DevCol& col, int L, int max_distance, int64_t max_len, uint32_t* cid, int64_t* n_clusters,
                  hipStream_t s);
 
 // ------------------------------------------------ UMI correction (correct.hip)
@@ -426,19 +425,17 @@ int cluster_summary_set_method(int m);
 // any device string column: n_reads / n_distinct / rep_row[n_clusters] (a row that holds the
 // cluster's representative; -1 for a cluster without rows). Synchronises s (row counts);
 // ROGTK_E_INVALID when a non-null row's id is >= n_clusters.
-int cluster_summary_general(const void* offsets, int ow, const uint8_t* values, const uint8_t* validity, int64_t voff,
-                            int64_t n, int L, const uint32_t* ids, int64_t n_clusters, int64_t max_len,
+int cluster_summary_general(const DevCol& col, int L, const uint32_t* ids, int64_t n_clusters, int64_t max_len,
                             uint32_t* n_reads, uint32_t* n_distinct, int64_t* rep_row, hipStream_t s);
 // the representatives as a string column: measure (out_offsets[n_clusters + 1]) then fill
 int representatives_temp(int64_t n_clusters, int64_t* bytes);
-int representatives_measure(const void* offsets, int ow, const int64_t* rep_row, int64_t n_clusters,
-                            int64_t* out_offsets, void* temp, int64_t temp_bytes, hipStream_t s);
+int representatives_measure(const DevCol& col, const int64_t* rep_row, int64_t n_clusters, int64_t* out_offsets,
+                            void* temp, int64_t temp_bytes, hipStream_t s);
 int representatives_fill(const void* offsets, int ow, const uint8_t* values, const int64_t* rep_row, int64_t n_clusters,
                          const int64_t* out_offsets, uint8_t* out_values, hipStream_t s);
 // corrected values under the input's own offsets (ids computed by the library)
-int corrected_fill(const void* offsets, int ow, const uint8_t* values, const uint8_t* validity, int64_t voff,
-                   int64_t n, const uint32_t* ids, int64_t n_clusters, const int64_t* rep_row, uint8_t* out_values,
-                   hipStream_t s);
+int corrected_fill(const DevCol& col, const uint32_t* ids, int64_t n_clusters, const int64_t* rep_row,
+                   uint8_t* out_values, hipStream_t s);
 
 // ------------------------------------- directional UMI clustering (directional.hip)
 // D[m] ascending distinct codes, C[m] their row counts (device): root[m] (index into D),
@@ -463,16 +460,14 @@ int directional_codes(const uint64_t* D, const uint32_t* C, int64_t m, int L, ui
 // by exact bytes; 0xFFFFFFFF for null rows), root_code[n] (nullable: the code of the row's
 // root, all ones for a row that is not regular); *longest (nullable) = the byte length of the
 // longest non-null row. Synchronises s.
-int directional_cluster(const void* offsets, int ow, const uint8_t* values, const uint8_t* validity, int64_t voff,
-                        int64_t n, int L, uint32_t* cluster_id, uint64_t* root_code, int64_t* n_clusters,
+int directional_cluster(const DevCol& col, int L, uint32_t* cluster_id, uint64_t* root_code, int64_t* n_clusters,
                         int64_t* rounds, int64_t* longest, hipStream_t s);
 
 // ------------------------------------- grouped UMI clustering (grouped.hip)
 // As directional_cluster with one u32 key per row (groups, device): two rows share a cluster
 // only under equal keys. max_distance 1: the directional rule per key; 0: the distinct (key,
 // string) pairs. cluster_group[n] (nullable, device): the key of every cluster. Synchronises s.
-int grouped_cluster(const void* offsets, int ow, const uint8_t* values, const uint8_t* validity, int64_t voff,
-                    int64_t n, int L, const uint32_t* groups, int max_distance, uint32_t* cluster_id,
+int grouped_cluster(const DevCol& col, int L, const uint32_t* groups, int max_distance, uint32_t* cluster_id,
                     uint64_t* root_code, uint32_t* cluster_group, int64_t* n_clusters, int64_t* rounds,
                     int64_t* longest, hipStream_t s);
 // how the grouped edge search finds its window (kWindow*; measurements only)
@@ -498,8 +493,7 @@ int barcode_whitelist_info(const void* handle, int64_t* W, int* L, int* prefix_d
 // a device string column against the whitelist. count_only: the exact pass alone, adding into
 // exact_counts (index / status / counts unused). Otherwise exact_counts and counts (both
 // nullable) are overwritten. totals5 on the host. Synchronises s.
-int barcode_correct(const void* handle, const void* offsets, int ow, const uint8_t* values, const uint8_t* validity,
-                    int64_t voff, int64_t n, int ambiguous, const uint32_t* prior_counts, uint32_t* index,
+int barcode_correct(const void* handle, const DevCol& col, int ambiguous, const uint32_t* prior_counts, uint32_t* index,
                     uint8_t* status, uint32_t* exact_counts, uint32_t* counts, bool count_only, int64_t* totals5,
                     hipStream_t s);
 // the corrected strings: out_offsets[n + 1] = scan of (status <= 1 ? L : 0), then the bytes

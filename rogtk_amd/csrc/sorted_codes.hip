@@ -21,6 +21,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "column_util.h"
+#include "level2.h"
 
 namespace rogtk {
 namespace {
@@ -237,14 +238,15 @@ int run(const void* offs, const uint8_t* vals, const uint8_t* validity, int64_t 
 
 }  // namespace
 
-int sorted_distinct_codes(const void* offsets, int ow, const uint8_t* values, const uint8_t* validity, int64_t voff,
-                          int64_t n, int L, bool want_counts, const ExtraCodeBytes* extra, uint32_t* cluster_id,
+int sorted_distinct_codes(const DevCol& col, int L, bool want_counts, const ExtraCodeBytes* extra, uint32_t* cluster_id,
                           SortedCodes* out, hipStream_t s, const uint32_t* groups) {
+    const int ow = col.ow;
+    const int64_t n = col.n;
     ROGTK_REQUIRE(n > 0 && n < (1ll << 31), ROGTK_E_UNSUPPORTED, "sorted codes: n %lld outside 1..2^31-1",
                   (long long)n);
     auto go = [&](auto ow_tag, auto key_tag, auto grouped_tag) {
         return run<decltype(ow_tag)::value, decltype(key_tag), decltype(grouped_tag)::value>(
-            offsets, values, validity, voff, n, L, want_counts, extra, cluster_id, out, s, groups);
+            col.offsets, col.values, col.validity, col.voff, n, L, want_counts, extra, cluster_id, out, s, groups);
     };
     using W4 = std::integral_constant<int, 4>;
     using W8 = std::integral_constant<int, 8>;
