@@ -1224,11 +1224,7 @@ int rogtk_bam_open_range(const char* path, int n_threads, int64_t c_begin, int64
                   "bam range: bad range [%lld, %lld) / skip %lld", (long long)c_begin, (long long)c_end,
                   (long long)skip);
     *reader = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        set_error("no HIP device available (librogtk_hip needs an MI355X / gfx950 GPU)");
-        return ROGTK_E_NODEVICE;
-    }
+    if (int rc = require_device()) return rc;
     std::unique_ptr<BamReader> R(new BamReader());
     R->z.f = fopen(path, "rb");
     ROGTK_REQUIRE(R->z.f, ROGTK_E_INVALID, "Failed to open BAM file '%s'", path);

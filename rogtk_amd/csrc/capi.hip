@@ -3,9 +3,8 @@
 //
 // Host-side responsibilities: argument validation, thread-local last-error,
 // the glibc-log2 entropy tables (bit-exact with the reference's f64::log2),
-// Hamming target encoding, launch-bracketing profiling events, and the definitions of what
-// level2.h declares: the per-thread device context of the level-2 (host Arrow buffer) entry
-// points, the upload of a host column and the checks those entries share.
+// Hamming target encoding and launch-bracketing profiling events. The level-2 (host Arrow
+// buffer) entries here stand on the shared layer of level2.h (level2.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,9 +14,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
-#include <memory>
 #include <mutex>
-#include <thread>
 #include <vector>
 
 #include "level2.h"
@@ -331,11 +328,6 @@ using namespace rogtk;
 
 namespace {
 
-int check_offset_width(int ow) {
-    ROGTK_REQUIRE(ow == 4 || ow == 8, ROGTK_E_INVALID, "offset_width must be 4 or 8, got %d", ow);
-    return ROGTK_OK;
-}
-
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 int check_packed_alignment(const uint32_t* codes, const ScoreOut& o, const uint32_t* hd) {
@@ -346,230 +338,7 @@ int check_packed_alignment(const uint32_t* codes, const ScoreOut& o, const uint3
     return ROGTK_OK;
 }
 
-// --------------------------------------------- per-thread level-2 context (level2.h)
-constexpr size_t kStageChunk = (size_t)32 << 20;
-
-int host_copy_threads() {
-    static const int t = [] {
-        const char* e = getenv("OMP_NUM_THREADS");
-        int v = e ? atoi(e) : 0;
-        const int hw = (int)std::thread::hardware_concurrency();
-        if (v <= 0) v = hw > 0 ? hw : 4;
-        return std::max(1, std::min(v, 8));
-    }();
-    return t;
-}
-
-void par_memcpy(void* dst, const void* src, size_t bytes) {
-    const int t = bytes >= ((size_t)4 << 20) ? host_copy_threads() : 1;
-    if (t <= 1) {
-        std::memcpy(dst, src, bytes);
-        return;
-    }
-    std::vector<std::thread> pool;
-    const size_t per = (bytes / t + 4095) / 4096 * 4096;
-    for (int k = 0; k < t; ++k) {
-        const size_t a = std::min(bytes, per * k), b = std::min(bytes, per * (k + 1));
-        if (a < b) pool.emplace_back([=] { std::memcpy((uint8_t*)dst + a, (const uint8_t*)src + a, b - a); });
-    }
-    for (auto& th : pool) th.join();
-}
-
-bool is_pinned(const void* p) {
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return a.type == hipMemoryTypeHost;
-}
-
-thread_local std::unique_ptr<HostCtx> t_ctx;
-
-// Longest row of a device column (irregular rows' radix-sort / byte-path width).
-template <class O>
-__global__ void k_max_len(const O* __restrict__ off, int64_t n, unsigned long long* out) {
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned long long m = 0;
-    if (r < n) m = (unsigned long long)((int64_t)off[r + 1] - (int64_t)off[r]);
-    for (int d = 32; d; d >>= 1) m = max(m, (unsigned long long)__shfl_xor(m, d));
-    if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
-}
-
 }  // namespace
-
-namespace rogtk {
-
-HostCtx::~HostCtx() {
-    for (int k = 0; k < 2; ++k) {
-        if (pin[k]) hipHostFree(pin[k]);
-        if (ev[k]) hipEventDestroy(ev[k]);
-    }
-    if (stream) hipStreamDestroy(stream);
-}
-
-int HostCtx::staging() {
-    for (int k = 0; k < 2; ++k) {
-        if (!pin[k]) ROGTK_HIP_CHECK(hipHostMalloc(&pin[k], kStageChunk, hipHostMallocDefault));
-        if (!ev[k]) ROGTK_HIP_CHECK(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
-    }
-    return ROGTK_OK;
-}
-
-int HostCtx::d2h(void* dst, const void* src, size_t bytes) {
-    if (bytes == 0) return ROGTK_OK;
-    if (is_pinned(dst)) {
-        ROGTK_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream));
-        ROGTK_HIP_CHECK(hipStreamSynchronize(stream));
-        return ROGTK_OK;
-    }
-    if (int rc = staging()) return rc;
-    size_t prev_off = 0, prev_len = 0;
-    int k = 0;
-    for (size_t off = 0; off < bytes; off += kStageChunk, k ^= 1) {
-        const size_t len = std::min(kStageChunk, bytes - off);
-        ROGTK_HIP_CHECK(hipMemcpyAsync(pin[k], (const uint8_t*)src + off, len, hipMemcpyDeviceToHost, stream));
-        ROGTK_HIP_CHECK(hipEventRecord(ev[k], stream));
-        if (off > 0) {  // the previous chunk: out of its staging buffer while this one moves
-            ROGTK_HIP_CHECK(hipEventSynchronize(ev[k ^ 1]));
-            par_memcpy((uint8_t*)dst + prev_off, pin[k ^ 1], prev_len);
-        }
-        prev_off = off;
-        prev_len = len;
-    }
-    ROGTK_HIP_CHECK(hipEventSynchronize(ev[k ^ 1]));
-    par_memcpy((uint8_t*)dst + prev_off, pin[k ^ 1], prev_len);
-    return ROGTK_OK;
-}
-
-int HostCtx::h2d(void* dst, const void* src, size_t bytes) {
-    if (bytes == 0) return ROGTK_OK;
-    if (is_pinned(src)) {
-        ROGTK_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream));
-        return ROGTK_OK;
-    }
-    if (int rc = staging()) return rc;
-    int k = 0;
-    int64_t i = 0;
-    for (size_t off = 0; off < bytes; off += kStageChunk, k ^= 1, ++i) {
-        const size_t len = std::min(kStageChunk, bytes - off);
-        if (i >= 2) ROGTK_HIP_CHECK(hipEventSynchronize(ev[k]));  // its DMA of two chunks ago is done
-        par_memcpy(pin[k], (const uint8_t*)src + off, len);
-        ROGTK_HIP_CHECK(hipMemcpyAsync((uint8_t*)dst + off, pin[k], len, hipMemcpyHostToDevice, stream));
-        ROGTK_HIP_CHECK(hipEventRecord(ev[k], stream));
-    }
-    // the staging buffers are reused by the next transfer only after these DMAs: every
-    // later use first waits on the events above (or the stream is synchronised)
-    ROGTK_HIP_CHECK(hipStreamSynchronize(stream));
-    return ROGTK_OK;
-}
-
-int host_ctx(HostCtx** out) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-        set_error("no HIP device available (librogtk_hip needs an MI355X / gfx950 GPU)");
-        return ROGTK_E_NODEVICE;
-    }
-    int dev = 0;
-    ROGTK_HIP_CHECK(hipGetDevice(&dev));
-    if (!t_ctx || t_ctx->device != dev) {
-        t_ctx.reset(new HostCtx());
-        t_ctx->device = dev;
-        ROGTK_HIP_CHECK(hipStreamCreateWithFlags(&t_ctx->stream, hipStreamNonBlocking));
-    }
-    *out = t_ctx.get();
-    return ROGTK_OK;
-}
-
-int launch_max_len(const void* offsets, int ow, int64_t n, unsigned long long* slot, hipStream_t s) {
-    const dim3 g((unsigned)((n + 255) / 256));
-    if (ow == 4)
-        hipLaunchKernelGGL(k_max_len<int32_t>, g, dim3(256), 0, s, (const int32_t*)offsets, n, slot);
-    else
-        hipLaunchKernelGGL(k_max_len<int64_t>, g, dim3(256), 0, s, (const int64_t*)offsets, n, slot);
-    ROGTK_HIP_CHECK(hipGetLastError());
-    return ROGTK_OK;
-}
-
-int column_max_len(const void* offsets, int ow, int64_t n, unsigned long long* slot, hipStream_t s, int64_t* out) {
-    ROGTK_HIP_CHECK(hipMemsetAsync(slot, 0, 8, s));
-    if (int rc = launch_max_len(offsets, ow, n, slot, s)) return rc;
-    unsigned long long h = 0;
-    ROGTK_HIP_CHECK(hipMemcpyAsync(&h, slot, 8, hipMemcpyDeviceToHost, s));
-    ROGTK_HIP_CHECK(hipStreamSynchronize(s));
-    *out = (int64_t)h;
-    return ROGTK_OK;
-}
-
-int device_max_len(HostCtx* c, int ow, int64_t n, int64_t* out) {
-    if (int rc = c->nirr.ensure(16)) return rc;
-    return column_max_len(c->offsets.p, ow, n, c->nirr.as<unsigned long long>() + 1, c->stream, out);
-}
-
-int check_rows_and_clusters(const char* name, int64_t n, int64_t n_clusters) {
-    ROGTK_REQUIRE(n >= 0 && n < (1ll << 31), ROGTK_E_UNSUPPORTED, "%s: n %lld outside 0..2^31-1", name, (long long)n);
-    ROGTK_REQUIRE(n_clusters >= 0 && n_clusters < (1ll << 32) - 1, ROGTK_E_INVALID, "%s: bad n_clusters %lld", name,
-                  (long long)n_clusters);
-    return ROGTK_OK;
-}
-
-int upload_col(HostCtx* c, const HostCol& h) {
-    const int64_t n = h.n;
-    ROGTK_REQUIRE(h.off(n) <= h.values_len || h.values_len < 0, ROGTK_E_INVALID,
-                  "offsets reference %lld bytes but values_len is %lld", (long long)h.off(n), (long long)h.values_len);
-    if (int rc = c->offsets.ensure((size_t)(n + 1) * h.ow)) return rc;
-    if (int rc = c->h2d(c->offsets.p, h.offsets, (size_t)(n + 1) * h.ow)) return rc;
-    // values: [0, off(n)), so the device offsets stay valid as given
-    if (int rc = c->values.ensure((size_t)std::max<int64_t>(h.off(n), 1))) return rc;
-    if (int rc = c->h2d(c->values.p, h.values, (size_t)h.off(n))) return rc;
-    if (h.validity) {
-        const size_t vb = (size_t)((h.voff + n + 7) / 8);
-        if (int rc = c->validity.ensure(vb)) return rc;
-        if (int rc = c->h2d(c->validity.p, h.validity, vb)) return rc;
-    }
-    return ROGTK_OK;
-}
-
-int stage_uploaded(HostCtx* c, const DevCol& col, int L, int64_t* n_irr, hipStream_t s) {
-    const int64_t n = col.n, words = (n + 63) / 64;
-    if (c->codes.ensure((size_t)std::max<int64_t>(n, 4) * 4) != ROGTK_OK ||
-        c->regbits.ensure((size_t)std::max<int64_t>(words, 1) * 8) != ROGTK_OK ||
-        c->irr.ensure((size_t)std::max<int64_t>(n, 1) * 8) != ROGTK_OK || c->nirr.ensure(16) != ROGTK_OK)
-        return ROGTK_E_HIP;
-    ROGTK_HIP_CHECK(hipMemsetAsync(c->nirr.p, 0, 16, s));
-    if (int rc = launch_stage(col.offsets, col.ow, col.values, col.validity, col.voff, n, L, c->codes.as<uint32_t>(),
-                              c->regbits.as<uint64_t>(), c->irr.as<int64_t>(), c->nirr.as<unsigned long long>(), s))
-        return rc;
-    if (n_irr) {
-        ROGTK_HIP_CHECK(hipMemcpyAsync(n_irr, c->nirr.p, 8, hipMemcpyDeviceToHost, s));
-        ROGTK_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    return ROGTK_OK;
-}
-
-int check_host_col(const HostCol& h) {
-    if (int rc = check_offset_width(h.ow)) return rc;
-    ROGTK_REQUIRE(h.n >= 0, ROGTK_E_INVALID, "n must be >= 0");
-    ROGTK_REQUIRE(h.offsets != nullptr, ROGTK_E_INVALID, "offsets must not be NULL");
-    ROGTK_REQUIRE(h.values != nullptr || h.off(h.n) == h.off0(), ROGTK_E_INVALID, "values must not be NULL");
-    ROGTK_REQUIRE(h.off0() == 0, ROGTK_E_INVALID,
-                  "offsets[0] must be 0 (slice the values buffer instead of the offsets)");
-    return ROGTK_OK;
-}
-
-int empty_str_result(int64_t n, rogtk_str_result* out) {
-    const int64_t words = std::max<int64_t>((n + 63) / 64, 1);
-    out->n = n;
-    out->offsets = (int64_t*)calloc((size_t)n + 1, 8);
-    out->values = (uint8_t*)calloc(1, 1);
-    out->validity = (uint8_t*)calloc((size_t)words, 8);
-    out->values_len = 0;
-    out->null_count = 0;
-    ROGTK_REQUIRE(out->offsets && out->values && out->validity, ROGTK_E_INVALID, "out of host memory");
-    return ROGTK_OK;
-}
-
-}  // namespace rogtk
 
 namespace rogtk {
 namespace detail_attach {
@@ -615,12 +384,7 @@ constexpr size_t kPinCacheMax = (size_t)16 << 30;
 
 int rogtk_host_alloc(size_t bytes, void** out) {
     ROGTK_REQUIRE(out, ROGTK_E_INVALID, "host_alloc: NULL out");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        set_error("no HIP device available (librogtk_hip needs an MI355X / gfx950 GPU)");
-        return ROGTK_E_NODEVICE;
-    }
+    if (int rc = require_device()) return rc;
     const size_t cls = (std::max<size_t>(bytes, 1) + ((size_t)2 << 20) - 1) / ((size_t)2 << 20) * ((size_t)2 << 20);
     {
         std::lock_guard<std::mutex> lk(g_pin_mu);
@@ -893,13 +657,14 @@ int rogtk_umi_complexity_host(const void* offsets, int offset_width, const uint8
     if (n == 0) return ROGTK_OK;
     HostCtx* c;
     if (int rc = host_ctx(&c)) return rc;
-    if (int rc = upload_col(c, h)) return rc;
+    DevCol col;
+    if (int rc = upload_col(c, 0, h, &col)) return rc;
     const int L = h.first_len();
     int64_t n_irr = 0;
-    if (int rc = stage_uploaded(c, DevCol(c, h), L, &n_irr, c->stream)) return rc;
+    if (int rc = stage_uploaded(c, col, L, &n_irr, c->stream)) return rc;
     int64_t max_len = 0;  // only the byte path (irregular rows) needs it
     if (n_irr > 0)
-        if (int rc = device_max_len(c, offset_width, n, &max_len)) return rc;
+        if (int rc = device_max_len(c, col, &max_len)) return rc;
     const ScoreOut ho = to_score_out(out);
     // device outputs
     double* dptr[6] = {nullptr};
@@ -922,7 +687,7 @@ int rogtk_umi_complexity_host(const void* offsets, int offset_width, const uint8
         if (rc) return rc;
     }
     if (n_irr > 0) {
-        int rc = rogtk_umi_score_rows(c->offsets.p, offset_width, c->values.as<uint8_t>(),
+        int rc = rogtk_umi_score_rows(col.offsets, col.ow, col.values,
                                       c->irr.as<int64_t>(), nullptr, n_irr, max_len, &ds, nullptr, 0,
                                       0, nullptr, nullptr, c->stream);
         if (rc) return rc;
@@ -948,13 +713,14 @@ int rogtk_hamming_host(const void* offsets, int offset_width, const uint8_t* val
     const uint8_t* tg = target ? target : &kEmpty;
     HostCtx* c;
     if (int rc = host_ctx(&c)) return rc;
-    if (int rc = upload_col(c, h)) return rc;
+    DevCol col;
+    if (int rc = upload_col(c, 0, h, &col)) return rc;
     const int L = h.first_len();
     int64_t n_irr = 0;
-    if (int rc = stage_uploaded(c, DevCol(c, h), L, &n_irr, c->stream)) return rc;
+    if (int rc = stage_uploaded(c, col, L, &n_irr, c->stream)) return rc;
     int64_t max_len = 0;  // only the byte path (irregular rows) needs it
     if (n_irr > 0)
-        if (int rc = device_max_len(c, offset_width, n, &max_len)) return rc;
+        if (int rc = device_max_len(c, col, &max_len)) return rc;
     uint32_t* dd = nullptr;
     uint64_t* dw = nullptr;
     if (distance) {
@@ -974,7 +740,7 @@ int rogtk_hamming_host(const void* offsets, int offset_width, const uint8_t* val
         ROGTK_HIP_CHECK(hipMemsetAsync(dw, 0, (size_t)words * 8, c->stream));
     }
     if (n_irr > 0) {
-        int rc = rogtk_umi_score_rows(c->offsets.p, offset_width, c->values.as<uint8_t>(),
+        int rc = rogtk_umi_score_rows(col.offsets, col.ow, col.values,
                                       c->irr.as<int64_t>(), nullptr, n_irr, max_len, nullptr, tg,
                                       target_len, max_distance, dd, dw, c->stream);
         if (rc) return rc;
@@ -1073,10 +839,11 @@ int rogtk_barcode_count_host(const void* handle, const rogtk_str_col* col, uint3
     if (int rc = check_host_col(h)) return rc;
     HostCtx* c;
     if (int rc = host_ctx(&c)) return rc;
-    if (int rc = upload_col(c, h)) return rc;
+    DevCol dcol;
+    if (int rc = upload_col(c, 0, h, &dcol)) return rc;
     if (int rc = c->out[1].ensure((size_t)W * 4)) return rc;
     if (int rc = c->h2d(c->out[1].p, exact_counts, (size_t)W * 4)) return rc;
-    if (int rc = barcode_correct(handle, DevCol(c, h), ROGTK_BC_COUNTS, nullptr, nullptr, nullptr,
+    if (int rc = barcode_correct(handle, dcol, ROGTK_BC_COUNTS, nullptr, nullptr, nullptr,
                                  c->out[1].as<uint32_t>(), nullptr, true, totals5, c->stream))
         return rc;
     return c->d2h(exact_counts, c->out[1].p, (size_t)W * 4);
@@ -1097,7 +864,8 @@ int rogtk_barcode_correct_host(const void* handle, const rogtk_str_col* col, int
     HostCtx* c;
     if (int rc = host_ctx(&c)) return rc;
     auto run = [&]() -> int {
-        if (int rc = upload_col(c, h)) return rc;
+        DevCol dcol;
+        if (int rc = upload_col(c, 0, h, &dcol)) return rc;
         const int64_t n1 = std::max<int64_t>(n, 1);
         if (c->out[0].ensure((size_t)n1 * 4) || c->out[1].ensure((size_t)W * 4) || c->out[2].ensure((size_t)W * 4) ||
             c->out[3].ensure((size_t)W * 4) || c->out[7].ensure((size_t)n1))
@@ -1106,7 +874,7 @@ int rogtk_barcode_correct_host(const void* handle, const rogtk_str_col* col, int
         uint8_t* d_status = c->out[7].as<uint8_t>();
         if (prior_counts)
             if (int rc = c->h2d(c->out[3].p, prior_counts, (size_t)W * 4)) return rc;
-        if (int rc = barcode_correct(handle, DevCol(c, h), ambiguous, prior_counts ? c->out[3].as<uint32_t>() : nullptr,
+        if (int rc = barcode_correct(handle, dcol, ambiguous, prior_counts ? c->out[3].as<uint32_t>() : nullptr,
                                      d_index, d_status,
                                      c->out[1].as<uint32_t>(), c->out[2].as<uint32_t>(), false, totals5, c->stream))
             return rc;
@@ -1119,33 +887,22 @@ int rogtk_barcode_correct_host(const void* handle, const rogtk_str_col* col, int
         if (counts)
             if (int rc = c->d2h(counts, c->out[2].p, (size_t)W * 4)) return rc;
         if (!corrected) return ROGTK_OK;
-        if (int rc = empty_str_result(n, corrected)) return rc;
-        for (int64_t i = 0; i < n; ++i) {
-            if (status[i] <= ROGTK_BC_CORRECTED) corrected->validity[i >> 3] |= (uint8_t)(1u << (i & 7));
-            else ++corrected->null_count;
-        }
-        if (n == 0) return ROGTK_OK;
+        if (n == 0) return empty_str_result(0, corrected);
         int64_t tb = 0;
         if (int rc = barcode_corrected_temp(n, &tb)) return rc;
         if (c->out[4].ensure((size_t)(n + 1) * 8) || c->out[5].ensure((size_t)tb)) return ROGTK_E_HIP;
         if (int rc = barcode_corrected_measure(handle, d_status, n, c->out[4].as<int64_t>(), c->out[5].p, tb,
                                                c->stream))
             return rc;
-        if (int rc = c->d2h(corrected->offsets, c->out[4].p, (size_t)(n + 1) * 8)) return rc;
-        const int64_t total = corrected->offsets[n];
-        if (total > 0) {
-            free(corrected->values);
-            corrected->values = (uint8_t*)malloc((size_t)total);
-            ROGTK_REQUIRE(corrected->values, ROGTK_E_INVALID, "out of host memory for %lld output bytes",
-                          (long long)total);
-            corrected->values_len = total;
-            if (c->out[6].ensure((size_t)total)) return ROGTK_E_HIP;
-            if (int rc = barcode_corrected_fill(handle, d_index, d_status, n, c->out[4].as<int64_t>(),
-                                                c->out[6].as<uint8_t>(), c->stream))
-                return rc;
-            if (int rc = c->d2h(corrected->values, c->out[6].p, (size_t)total)) return rc;
-        }
-        return ROGTK_OK;
+        if (int rc = str_result_begin(c, n, c->out[4].as<int64_t>(), nullptr, nullptr, corrected)) return rc;
+        for (int64_t i = 0; i < n; ++i)
+            if (status[i] > ROGTK_BC_CORRECTED) str_result_set_null(corrected, i);
+        return str_result_finish(
+            c, c->out[6],
+            [&](uint8_t* d) {
+                return barcode_corrected_fill(handle, d_index, d_status, n, c->out[4].as<int64_t>(), d, c->stream);
+            },
+            corrected);
     };
     const int rc = run();
     if (rc && corrected) rogtk_str_result_free(corrected);

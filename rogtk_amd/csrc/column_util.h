@@ -42,6 +42,11 @@ __device__ __forceinline__ bool row_valid(const uint8_t* validity, int64_t voff,
     return (validity[b >> 3] >> (b & 7)) & 1;
 }
 
+// offset i of a column whose offset width is only known at run time (ow 4 or 8)
+__device__ __forceinline__ int64_t row_off(const void* offsets, int ow, int64_t i) {
+    return ow == 4 ? (int64_t)((const int32_t*)offsets)[i] : ((const int64_t*)offsets)[i];
+}
+
 // One stream-ordered allocation handed out in 256-byte aligned pieces; released behind the
 // work already enqueued on the stream. The caller sizes get() as the sum of al() of its takes;
 // a take past that sum stops the program.

@@ -47,12 +47,12 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
-#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 
-#include "rogtk_internal.h"
+#include "column_util.h"
+#include "level2.h"
 
 namespace {
 
@@ -194,15 +194,6 @@ std::vector<uint32_t> build_blob(const rogtk_fuzzy_program& p) {
 }
 
 // ------------------------------------------------------------------ device
-struct FzCol {
-    const void* off;
-    int ow;
-    const uint8_t* val;
-    const uint8_t* valid;
-    int64_t voff;
-    int64_t n;
-};
-
 constexpr int kWin = 256;  // bytes of the row staged in LDS per wave and 64-start chunk
 
 struct Prog {  // the program in LDS, and this wave's window
@@ -214,14 +205,6 @@ struct Prog {  // the program in LDS, and this wave's window
     int ref_len;
 };
 
-__device__ __forceinline__ int64_t fz_off(const FzCol& c, int64_t i) {
-    return c.ow == 4 ? (int64_t)((const int32_t*)c.off)[i] : ((const int64_t*)c.off)[i];
-}
-__device__ __forceinline__ bool fz_valid(const FzCol& c, int64_t i) {
-    if (!c.valid) return true;
-    const int64_t b = c.voff + i;
-    return (c.valid[b >> 3] >> (b & 7)) & 1;
-}
 __device__ __forceinline__ int cp_width(uint8_t b) { return b < 0x80 ? 1 : b < 0xE0 ? 2 : b < 0xF0 ? 3 : 4; }
 
 // All threads of the block: blob head + alternatives + atoms into LDS. The windows of the
@@ -386,15 +369,15 @@ struct RowWord {
     uint64_t valid;
     int rows;
 };
-__device__ __forceinline__ RowWord load_word(const FzCol& col, int64_t w) {
+__device__ __forceinline__ RowWord load_word(const DevCol& col, int64_t w) {
     const int lane = threadIdx.x & 63;
     const int64_t i = w * 64 + lane;
     RowWord r{0, 0, 0, (int)min((int64_t)64, col.n - w * 64)};
     bool ok = false;
     if (i < col.n) {
-        ok = fz_valid(col, i);
-        r.a = fz_off(col, i);
-        r.b = fz_off(col, i + 1);
+        ok = row_valid(col.validity, col.voff, i);
+        r.a = row_off(col.offsets, col.ow, i);
+        r.b = row_off(col.offsets, col.ow, i + 1);
     }
     r.valid = __ballot(ok);
     return r;
@@ -402,7 +385,7 @@ __device__ __forceinline__ RowWord load_word(const FzCol& col, int64_t w) {
 
 extern __shared__ uint32_t fz_lds[];
 
-__global__ __launch_bounds__(kBlock) void k_fuzzy_contains(const uint32_t* __restrict__ blob, FzCol col,
+__global__ __launch_bounds__(kBlock) void k_fuzzy_contains(const uint32_t* __restrict__ blob, DevCol col,
                                                            uint64_t* __restrict__ out_bits,
                                                            uint64_t* __restrict__ out_valid) {
     const Prog p = load_program(blob, fz_lds);
@@ -416,7 +399,7 @@ __global__ __launch_bounds__(kBlock) void k_fuzzy_contains(const uint32_t* __res
             const int64_t a = __shfl(rw.a, r), b = __shfl(rw.b, r);
             if (!((rw.valid >> r) & 1)) continue;
             int64_t mb, me;
-            if (wave_search(p, col.val + a, b - a, 0, &mb, &me)) hits |= 1ull << r;
+            if (wave_search(p, col.values + a, b - a, 0, &mb, &me)) hits |= 1ull << r;
         }
         if (lane == 0) {
             out_bits[w] = hits;
@@ -425,7 +408,7 @@ __global__ __launch_bounds__(kBlock) void k_fuzzy_contains(const uint32_t* __res
     }
 }
 
-__global__ __launch_bounds__(kBlock) void k_fuzzy_replace_measure(const uint32_t* __restrict__ blob, FzCol col,
+__global__ __launch_bounds__(kBlock) void k_fuzzy_replace_measure(const uint32_t* __restrict__ blob, DevCol col,
                                                                   int replace_all, int64_t* __restrict__ lengths,
                                                                   uint64_t* __restrict__ out_valid) {
     const Prog p = load_program(blob, fz_lds);
@@ -439,7 +422,7 @@ __global__ __launch_bounds__(kBlock) void k_fuzzy_replace_measure(const uint32_t
         for (int r = 0; r < rw.rows; ++r) {
             const int64_t a = __shfl(rw.a, r), b = __shfl(rw.b, r);
             if (!((rw.valid >> r) & 1)) continue;
-            const uint8_t* s = col.val + a;
+            const uint8_t* s = col.values + a;
             const int64_t n = b - a;
             int64_t pos = 0, total = n, mb, me;
             while (wave_search(p, s, n, pos, &mb, &me)) {
@@ -458,7 +441,7 @@ __device__ __forceinline__ void wave_copy(uint8_t* __restrict__ dst, const uint8
     for (int64_t j = threadIdx.x & 63; j < k; j += 64) dst[j] = src[j];
 }
 
-__global__ __launch_bounds__(kBlock) void k_fuzzy_replace_fill(const uint32_t* __restrict__ blob, FzCol col,
+__global__ __launch_bounds__(kBlock) void k_fuzzy_replace_fill(const uint32_t* __restrict__ blob, DevCol col,
                                                                int replace_all,
                                                                const int64_t* __restrict__ offsets,
                                                                uint8_t* __restrict__ out) {
@@ -474,7 +457,7 @@ __global__ __launch_bounds__(kBlock) void k_fuzzy_replace_fill(const uint32_t* _
         for (int r = 0; r < rw.rows; ++r) {
             const int64_t a = __shfl(rw.a, r), b = __shfl(rw.b, r), o0 = __shfl(my_o, r);
             if (!((rw.valid >> r) & 1)) continue;
-            const uint8_t* s = col.val + a;
+            const uint8_t* s = col.values + a;
             const int64_t n = b - a;
             uint8_t* o = out + o0;
             int64_t pos = 0, mb, me;
@@ -492,11 +475,11 @@ __global__ __launch_bounds__(kBlock) void k_fuzzy_replace_fill(const uint32_t* _
 }
 
 // ------------------------------------------------------------------ launch
-int to_col(const rogtk_str_col* c, FzCol* out) {
+int to_col(const rogtk_str_col* c, DevCol* out) {
     ROGTK_REQUIRE(c, ROGTK_E_INVALID, "null column");
     ROGTK_REQUIRE(c->offset_width == 4 || c->offset_width == 8, ROGTK_E_INVALID, "offset_width must be 4 or 8");
     ROGTK_REQUIRE(c->n >= 0 && c->n < ((int64_t)1 << 31) - 1, ROGTK_E_UNSUPPORTED, "at most 2^31 - 2 rows per call");
-    *out = FzCol{c->offsets, c->offset_width, c->values, c->validity, c->validity_offset, c->n};
+    *out = DevCol(c->offsets, c->offset_width, c->values, c->validity, c->validity_offset, c->n);
     return ROGTK_OK;
 }
 
@@ -542,63 +525,89 @@ void drop_device_copies(rogtk_fuzzy_program* p) {
     p->dev.clear();
 }
 
-// per-thread buffers of the host entry points
-struct FzCtx {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    DevBuf off, val, valid, bits, vbits, offsets, cub, out;
-    ~FzCtx() {
-        if (stream) hipStreamDestroy(stream);
-    }
-};
-thread_local std::unique_ptr<FzCtx> t_fz;
-
-int host_ctx(FzCtx** out) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        set_error("no HIP device available (librogtk_hip needs an MI355X / gfx950 GPU)");
-        return ROGTK_E_NODEVICE;
-    }
-    int dev = 0;
-    ROGTK_HIP_CHECK(hipGetDevice(&dev));
-    if (!t_fz || t_fz->device != dev) {
-        t_fz.reset(new FzCtx());
-        t_fz->device = dev;
-        ROGTK_HIP_CHECK(hipStreamCreateWithFlags(&t_fz->stream, hipStreamNonBlocking));
-    }
-    *out = t_fz.get();
+// the three launches on a checked column (to_col), for the device and the host entries
+int contains(rogtk_fuzzy_program* p, const DevCol& c, uint64_t* out_bits, uint64_t* out_valid_bits, hipStream_t s) {
+    ROGTK_REQUIRE(out_bits && out_valid_bits, ROGTK_E_INVALID, "null output pointer");
+    const uint32_t* blob;
+    uint32_t lds;
+    if (int rc = device_blob(p, s, &blob, &lds)) return rc;
+    if (c.n > 0)
+        hipLaunchKernelGGL(k_fuzzy_contains, dim3(grid_words(c.n)), dim3(kBlock), lds, s, blob, c, out_bits,
+                           out_valid_bits);
+    ROGTK_HIP_CHECK(hipGetLastError());
     return ROGTK_OK;
 }
 
-// Host column -> device column (int64 offsets rebased to 0, values [off(0), off(n))).
-int upload(FzCtx* c, const rogtk_str_col* h, rogtk_str_col* d) {
-    ROGTK_REQUIRE(h && h->offsets, ROGTK_E_INVALID, "null column");
-    ROGTK_REQUIRE(h->offset_width == 4 || h->offset_width == 8, ROGTK_E_INVALID, "offset_width must be 4 or 8");
-    ROGTK_REQUIRE(h->n >= 0 && h->n < ((int64_t)1 << 31) - 1, ROGTK_E_UNSUPPORTED, "at most 2^31 - 2 rows per call");
-    const int64_t n = h->n;
-    hipStream_t s = c->stream;
-    std::vector<int64_t> off64(n + 1);
-    for (int64_t r = 0; r <= n; ++r)
-        off64[r] = h->offset_width == 4 ? ((const int32_t*)h->offsets)[r] : ((const int64_t*)h->offsets)[r];
-    const int64_t base = off64[0], vb = off64[n] - base;
-    for (int64_t r = 0; r < n; ++r)
-        ROGTK_REQUIRE(off64[r] <= off64[r + 1], ROGTK_E_INVALID, "offsets decrease at row %lld", (long long)r);
-    ROGTK_REQUIRE(base >= 0 && (h->values_len < 0 || off64[n] <= h->values_len), ROGTK_E_INVALID,
-                  "offsets reference bytes outside values");
-    for (int64_t r = 0; r <= n; ++r) off64[r] -= base;
-    if (c->off.ensure((size_t)(n + 1) * 8) || c->val.ensure((size_t)std::max<int64_t>(vb, 1))) return ROGTK_E_HIP;
-    ROGTK_HIP_CHECK(hipMemcpyAsync(c->off.p, off64.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));
-    if (vb > 0) ROGTK_HIP_CHECK(hipMemcpyAsync(c->val.p, h->values + base, (size_t)vb, hipMemcpyHostToDevice, s));
-    const uint8_t* dvalid = nullptr;
-    if (h->validity) {
-        const size_t nb = (size_t)((h->validity_offset + n + 7) / 8);
-        if (c->valid.ensure(std::max<size_t>(nb, 1))) return ROGTK_E_HIP;
-        ROGTK_HIP_CHECK(hipMemcpyAsync(c->valid.p, h->validity, nb, hipMemcpyHostToDevice, s));
-        dvalid = c->valid.as<uint8_t>();
-    }
-    ROGTK_HIP_CHECK(hipStreamSynchronize(s));  // off64 is a local
-    *d = rogtk_str_col{c->off.p, 8, c->val.as<uint8_t>(), vb, dvalid, h->validity_offset, n};
+int replace_measure(rogtk_fuzzy_program* p, const DevCol& c, int replace_all, int64_t* out_offsets,
+                    uint64_t* out_valid_bits, void* temp, int64_t temp_bytes, hipStream_t s) {
+    ROGTK_REQUIRE(out_offsets && out_valid_bits && temp, ROGTK_E_INVALID, "null output / temp pointer");
+    const uint32_t* blob;
+    uint32_t lds;
+    if (int rc = device_blob(p, s, &blob, &lds)) return rc;
+    // temp as rogtk_str_measure: lengths (n + 1 int64), then the scan's own storage
+    int64_t* lengths = (int64_t*)temp;
+    const size_t head = ((size_t)(c.n + 1) * 8 + 255) / 256 * 256;
+    size_t tb = 0;
+    ROGTK_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, lengths, out_offsets, (int)(c.n + 1), s));
+    ROGTK_REQUIRE((int64_t)(head + tb) <= temp_bytes, ROGTK_E_INVALID, "temp_bytes %lld too small (need %lld)",
+                  (long long)temp_bytes, (long long)(head + tb));
+    ROGTK_HIP_CHECK(hipMemsetAsync(lengths + c.n, 0, 8, s));
+    if (c.n > 0)
+        hipLaunchKernelGGL(k_fuzzy_replace_measure, dim3(grid_words(c.n)), dim3(kBlock), lds, s, blob, c,
+                           replace_all != 0, lengths, out_valid_bits);
+    ROGTK_HIP_CHECK(hipGetLastError());
+    ROGTK_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum((uint8_t*)temp + head, tb, lengths, out_offsets,
+                                                     (int)(c.n + 1), s));
     return ROGTK_OK;
+}
+
+int replace_fill(rogtk_fuzzy_program* p, const DevCol& c, int replace_all, const int64_t* offsets,
+                 uint8_t* out_values, hipStream_t s) {
+    ROGTK_REQUIRE(offsets && out_values, ROGTK_E_INVALID, "null offsets / output pointer");
+    const uint32_t* blob;
+    uint32_t lds;
+    if (int rc = device_blob(p, s, &blob, &lds)) return rc;
+    if (c.n > 0)
+        hipLaunchKernelGGL(k_fuzzy_replace_fill, dim3(grid_words(c.n)), dim3(kBlock), lds, s, blob, c,
+                           replace_all != 0, offsets, out_values);
+    ROGTK_HIP_CHECK(hipGetLastError());
+    return ROGTK_OK;
+}
+
+// What the host entries ask of their column before any device access: to_col's rules, and of
+// the offsets, which are host memory here, that they do not decrease and stay inside values.
+// A first offset above 0 (a slice) is accepted: upload_col rebases it.
+int check_host(const rogtk_str_col* h) {
+    ROGTK_REQUIRE(h && h->offsets, ROGTK_E_INVALID, "null column");
+    DevCol as_given;
+    if (int rc = to_col(h, &as_given)) return rc;
+    const HostCol c(*h);
+    for (int64_t r = 0; r < c.n; ++r)
+        ROGTK_REQUIRE(c.off(r) <= c.off(r + 1), ROGTK_E_INVALID, "offsets decrease at row %lld", (long long)r);
+    ROGTK_REQUIRE(c.off0() >= 0 && (c.values_len < 0 || c.off(c.n) <= c.values_len), ROGTK_E_INVALID,
+                  "offsets reference bytes outside values");
+    return ROGTK_OK;
+}
+
+// rogtk_fuzzy_replace_host after its checks. Scratch: out[4] the output offsets, out[5] the
+// scan's storage, out[6] the bytes, out[7] the validity words.
+int replace_host(HostCtx* c, rogtk_fuzzy_program* p, const rogtk_str_col* col, int replace_all, rogtk_str_result* out) {
+    hipStream_t s = c->stream;
+    DevCol d;
+    if (int rc = upload_col(c, 0, HostCol(*col), &d)) return rc;
+    const int64_t n = d.n;
+    int64_t tb = 0;
+    if (int rc = rogtk_str_temp_bytes(n, &tb)) return rc;
+    const int64_t words = std::max<int64_t>((n + 63) / 64, 1);
+    if (c->out[4].ensure((size_t)(n + 1) * 8) || c->out[5].ensure((size_t)tb) || c->out[7].ensure((size_t)words * 8))
+        return ROGTK_E_HIP;
+    int64_t* d_off = c->out[4].as<int64_t>();
+    uint64_t* d_valid = c->out[7].as<uint64_t>();
+    ROGTK_HIP_CHECK(hipMemsetAsync(d_valid, 0, (size_t)words * 8, s));
+    if (int rc = replace_measure(p, d, replace_all, d_off, d_valid, c->out[5].p, tb, s)) return rc;
+    if (int rc = str_result_begin(c, n, d_off, d_valid, nullptr, out)) return rc;
+    return str_result_finish(
+        c, c->out[6], [&](uint8_t* v) { return replace_fill(p, d, replace_all, d_off, v, s); }, out);
 }
 
 }  // namespace
@@ -730,128 +739,52 @@ int rogtk_fuzzy_describe(const rogtk_fuzzy_program* p, char* out, int64_t cap, i
 
 int rogtk_fuzzy_contains(rogtk_fuzzy_program* p, const rogtk_str_col* col, uint64_t* out_bits,
                          uint64_t* out_valid_bits, void* stream) {
-    FzCol c;
+    DevCol c;
     if (int rc = to_col(col, &c)) return rc;
-    ROGTK_REQUIRE(out_bits && out_valid_bits, ROGTK_E_INVALID, "null output pointer");
-    hipStream_t s = (hipStream_t)stream;
-    const uint32_t* blob;
-    uint32_t lds;
-    if (int rc = device_blob(p, s, &blob, &lds)) return rc;
-    if (c.n > 0)
-        hipLaunchKernelGGL(k_fuzzy_contains, dim3(grid_words(c.n)), dim3(kBlock), lds, s, blob, c, out_bits,
-                           out_valid_bits);
-    ROGTK_HIP_CHECK(hipGetLastError());
-    return ROGTK_OK;
+    return contains(p, c, out_bits, out_valid_bits, as_stream(stream));
 }
 
 int rogtk_fuzzy_replace_measure(rogtk_fuzzy_program* p, const rogtk_str_col* col, int replace_all,
                                 int64_t* out_offsets, uint64_t* out_valid_bits, void* temp, int64_t temp_bytes,
                                 void* stream) {
-    FzCol c;
+    DevCol c;
     if (int rc = to_col(col, &c)) return rc;
-    ROGTK_REQUIRE(out_offsets && out_valid_bits && temp, ROGTK_E_INVALID, "null output / temp pointer");
-    hipStream_t s = (hipStream_t)stream;
-    const uint32_t* blob;
-    uint32_t lds;
-    if (int rc = device_blob(p, s, &blob, &lds)) return rc;
-    // temp as rogtk_str_measure: lengths (n + 1 int64), then the scan's own storage
-    int64_t* lengths = (int64_t*)temp;
-    const size_t head = ((size_t)(c.n + 1) * 8 + 255) / 256 * 256;
-    size_t tb = 0;
-    ROGTK_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, lengths, out_offsets, (int)(c.n + 1), s));
-    ROGTK_REQUIRE((int64_t)(head + tb) <= temp_bytes, ROGTK_E_INVALID, "temp_bytes %lld too small (need %lld)",
-                  (long long)temp_bytes, (long long)(head + tb));
-    ROGTK_HIP_CHECK(hipMemsetAsync(lengths + c.n, 0, 8, s));
-    if (c.n > 0)
-        hipLaunchKernelGGL(k_fuzzy_replace_measure, dim3(grid_words(c.n)), dim3(kBlock), lds, s, blob, c,
-                           replace_all != 0, lengths, out_valid_bits);
-    ROGTK_HIP_CHECK(hipGetLastError());
-    ROGTK_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum((uint8_t*)temp + head, tb, lengths, out_offsets,
-                                                     (int)(c.n + 1), s));
-    return ROGTK_OK;
+    return replace_measure(p, c, replace_all, out_offsets, out_valid_bits, temp, temp_bytes, as_stream(stream));
 }
 
 int rogtk_fuzzy_replace_fill(rogtk_fuzzy_program* p, const rogtk_str_col* col, int replace_all,
                              const int64_t* offsets, uint8_t* out_values, void* stream) {
-    FzCol c;
+    DevCol c;
     if (int rc = to_col(col, &c)) return rc;
-    ROGTK_REQUIRE(offsets && out_values, ROGTK_E_INVALID, "null offsets / output pointer");
-    hipStream_t s = (hipStream_t)stream;
-    const uint32_t* blob;
-    uint32_t lds;
-    if (int rc = device_blob(p, s, &blob, &lds)) return rc;
-    if (c.n > 0)
-        hipLaunchKernelGGL(k_fuzzy_replace_fill, dim3(grid_words(c.n)), dim3(kBlock), lds, s, blob, c,
-                           replace_all != 0, offsets, out_values);
-    ROGTK_HIP_CHECK(hipGetLastError());
-    return ROGTK_OK;
+    return replace_fill(p, c, replace_all, offsets, out_values, as_stream(stream));
 }
 
 int rogtk_fuzzy_contains_host(rogtk_fuzzy_program* p, const rogtk_str_col* col, uint64_t* out_bits,
                               uint64_t* out_valid_bits) {
     ROGTK_REQUIRE(p && col && out_bits, ROGTK_E_INVALID, "null argument");
-    FzCtx* c;
+    if (int rc = check_host(col)) return rc;
+    HostCtx* c;
     if (int rc = host_ctx(&c)) return rc;
-    rogtk_str_col d;
-    if (int rc = upload(c, col, &d)) return rc;
+    DevCol d;
+    if (int rc = upload_col(c, 0, HostCol(*col), &d)) return rc;
     const int64_t words = (d.n + 63) / 64;
     if (words == 0) return ROGTK_OK;
-    if (c->bits.ensure((size_t)words * 8) || c->vbits.ensure((size_t)words * 8)) return ROGTK_E_HIP;
-    if (int rc = rogtk_fuzzy_contains(p, &d, c->bits.as<uint64_t>(), c->vbits.as<uint64_t>(), c->stream)) return rc;
-    ROGTK_HIP_CHECK(hipMemcpyAsync(out_bits, c->bits.p, (size_t)words * 8, hipMemcpyDeviceToHost, c->stream));
-    if (out_valid_bits)
-        ROGTK_HIP_CHECK(
-            hipMemcpyAsync(out_valid_bits, c->vbits.p, (size_t)words * 8, hipMemcpyDeviceToHost, c->stream));
-    ROGTK_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return ROGTK_OK;
+    if (c->out[0].ensure((size_t)words * 8) || c->out[7].ensure((size_t)words * 8)) return ROGTK_E_HIP;
+    if (int rc = contains(p, d, c->out[0].as<uint64_t>(), c->out[7].as<uint64_t>(), c->stream)) return rc;
+    if (int rc = c->d2h(out_bits, c->out[0].p, (size_t)words * 8)) return rc;
+    return out_valid_bits ? c->d2h(out_valid_bits, c->out[7].p, (size_t)words * 8) : ROGTK_OK;
 }
 
 int rogtk_fuzzy_replace_host(rogtk_fuzzy_program* p, const rogtk_str_col* col, int replace_all,
                              rogtk_str_result* out) {
     ROGTK_REQUIRE(p && col && out, ROGTK_E_INVALID, "null argument");
     *out = rogtk_str_result{};
-    FzCtx* c;
+    if (int rc = check_host(col)) return rc;
+    HostCtx* c;
     if (int rc = host_ctx(&c)) return rc;
-    hipStream_t s = c->stream;
-    rogtk_str_col d;
-    if (int rc = upload(c, col, &d)) return rc;
-    const int64_t n = d.n;
-    int64_t tb = 0;
-    if (int rc = rogtk_str_temp_bytes(n, &tb)) return rc;
-    const int64_t words = std::max<int64_t>((n + 63) / 64, 1);
-    if (c->cub.ensure((size_t)tb) || c->offsets.ensure((size_t)(n + 1) * 8) || c->vbits.ensure((size_t)words * 8))
-        return ROGTK_E_HIP;
-    ROGTK_HIP_CHECK(hipMemsetAsync(c->vbits.p, 0, (size_t)words * 8, s));
-    if (int rc = rogtk_fuzzy_replace_measure(p, &d, replace_all, c->offsets.as<int64_t>(), c->vbits.as<uint64_t>(),
-                                             c->cub.p, tb, s))
-        return rc;
-    int64_t* offs = (int64_t*)malloc((size_t)(n + 1) * 8);
-    uint8_t* bits = (uint8_t*)malloc((size_t)words * 8);
-    if (!offs || !bits) {
-        free(offs);
-        free(bits);
-        set_error("out of host memory");
-        return ROGTK_E_INVALID;
-    }
-    *out = rogtk_str_result{n, offs, nullptr, 0, bits, 0};
-    ROGTK_HIP_CHECK(hipMemcpyAsync(offs, c->offsets.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
-    ROGTK_HIP_CHECK(hipMemcpyAsync(bits, c->vbits.p, (size_t)words * 8, hipMemcpyDeviceToHost, s));
-    ROGTK_HIP_CHECK(hipStreamSynchronize(s));
-    const int64_t total = offs[n];
-    out->values = (uint8_t*)malloc((size_t)std::max<int64_t>(total, 1));
-    ROGTK_REQUIRE(out->values, ROGTK_E_INVALID, "out of host memory for %lld output bytes", (long long)total);
-    out->values_len = total;
-    if (total > 0) {
-        if (c->out.ensure((size_t)total)) return ROGTK_E_HIP;
-        if (int rc = rogtk_fuzzy_replace_fill(p, &d, replace_all, c->offsets.as<int64_t>(), c->out.as<uint8_t>(), s))
-            return rc;
-        ROGTK_HIP_CHECK(hipMemcpyAsync(out->values, c->out.p, (size_t)total, hipMemcpyDeviceToHost, s));
-        ROGTK_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    int64_t nulls = 0;
-    for (int64_t r = 0; r < n; ++r) nulls += !((bits[r >> 3] >> (r & 7)) & 1);
-    out->null_count = nulls;
-    return ROGTK_OK;
+    const int rc = replace_host(c, p, col, replace_all, out);
+    if (rc) rogtk_str_result_free(out);
+    return rc;
 }
 
 }  // extern "C"

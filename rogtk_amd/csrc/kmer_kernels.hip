@@ -2666,11 +2666,7 @@ struct KmerCtx {
 thread_local std::unique_ptr<KmerCtx> t_kctx;
 
 int kmer_ctx(KmerCtx** out) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-        set_error("no HIP device available (librogtk_hip needs an MI355X / gfx950 GPU)");
-        return ROGTK_E_NODEVICE;
-    }
+    if (int rc = require_device()) return rc;
     int dev = 0;
     ROGTK_HIP_CHECK(hipGetDevice(&dev));
     if (!t_kctx || t_kctx->device != dev) {

@@ -15,6 +15,8 @@ namespace rogtk {
 
 // ---------------------------------------------------------------- errors
 void set_error(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+// ROGTK_OK with a HIP device in the machine, else ROGTK_E_NODEVICE and its message (level2.hip)
+int require_device();
 
 #define ROGTK_HIP_CHECK(expr)                                                                    \
     do {                                                                                         \

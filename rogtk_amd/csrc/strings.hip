@@ -20,10 +20,9 @@
 #include <hipcub/hipcub.hpp>
 
 #include <cstdlib>
-#include <memory>
-#include <vector>
 
-#include "rogtk_internal.h"
+#include "column_util.h"
+#include "level2.h"
 #include "strings_rows.h"
 
 namespace rogtk {
@@ -33,6 +32,8 @@ using namespace str_rows;
 
 constexpr int kBlock = 256;
 
+// An input column as the kernels take it: a DevCol whose row count gives way to the
+// broadcast flag (the rows of a call are OpArgs::n).
 struct Col {
     const void* off;
     int ow;
@@ -41,24 +42,21 @@ struct Col {
     int64_t voff;
     int bcast;  // row 0 for every row (a length-1 column broadcast)
 };
+Col as_col(const DevCol& d, int64_t n_rows) {
+    return Col{d.offsets, d.ow, d.values, d.validity, d.voff, d.n == 1 && n_rows != 1 ? 1 : 0};
+}
 
 struct Cols {
     Col c[3];
 };
 
-__device__ __forceinline__ int64_t col_off(const Col& c, int64_t i) {
-    return c.ow == 4 ? (int64_t)((const int32_t*)c.off)[i] : ((const int64_t*)c.off)[i];
-}
 __device__ __forceinline__ bool col_valid(const Col& c, int64_t i) {
-    if (c.bcast) i = 0;
-    if (!c.valid) return true;
-    const int64_t b = c.voff + i;
-    return (c.valid[b >> 3] >> (b & 7)) & 1;
+    return row_valid(c.valid, c.voff, c.bcast ? 0 : i);
 }
 
 __device__ __forceinline__ Str col_str(const Col& c, int64_t i) {
     if (c.bcast) i = 0;
-    const int64_t a = col_off(c, i), b = col_off(c, i + 1);
+    const int64_t a = row_off(c.off, c.ow, i), b = row_off(c.off, c.ow, i + 1);
     return Str{c.val + a, (uint64_t)(b - a)};
 }
 
@@ -135,24 +133,67 @@ int make_args(int op, const rogtk_str_col* cols, int n_cols, int64_t n_rows, int
         ROGTK_REQUIRE(c.n == n_rows || c.n == 1, ROGTK_E_INVALID,
                       "input %d has %lld rows (expected %lld or a broadcast of 1)", k, (long long)c.n,
                       (long long)n_rows);
-        a->cols.c[k] = Col{c.offsets, c.offset_width, c.values, c.validity, c.validity_offset,
-                           c.n == 1 && n_rows != 1 ? 1 : 0};
+        a->cols.c[k] = as_col(DevCol(c.offsets, c.offset_width, c.values, c.validity, c.validity_offset, c.n), n_rows);
     }
     return ROGTK_OK;
 }
 
 inline unsigned grid_rows(int64_t n) { return (unsigned)std::max<int64_t>((n + kBlock - 1) / kBlock, 1); }
 
-// per-thread scan scratch of the host entry point
-struct StrCtx {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    DevBuf off[3], val[3], valid[3], lengths, offsets, bits, cub, out;
-    ~StrCtx() {
-        if (stream) hipStreamDestroy(stream);
+// the two passes over columns already checked (make_args), for the device and the host entries
+int measure(const OpArgs& a, int64_t* out_offsets, uint64_t* out_valid_bits, void* temp, int64_t temp_bytes,
+            hipStream_t s) {
+    const int64_t n_rows = a.n;
+    ROGTK_REQUIRE(n_rows < (int64_t)1 << 31, ROGTK_E_UNSUPPORTED, "at most 2^31 - 1 rows per call");
+    ROGTK_REQUIRE(out_offsets && out_valid_bits && temp, ROGTK_E_INVALID, "null output / temp pointer");
+    int64_t* lengths = (int64_t*)temp;
+    const size_t head = ((size_t)(n_rows + 1) * 8 + 255) / 256 * 256;
+    size_t tb = 0;
+    ROGTK_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, lengths, out_offsets, (int)(n_rows + 1), s));
+    ROGTK_REQUIRE((int64_t)(head + tb) <= temp_bytes, ROGTK_E_INVALID, "temp_bytes %lld too small (need %lld)",
+                  (long long)temp_bytes, (long long)(head + tb));
+    ROGTK_HIP_CHECK(hipMemsetAsync(lengths + n_rows, 0, 8, s));
+    if (n_rows > 0)
+        hipLaunchKernelGGL(k_str_measure, dim3(grid_rows(n_rows)), dim3(kBlock), 0, s, a, lengths, out_valid_bits);
+    ROGTK_HIP_CHECK(hipGetLastError());
+    ROGTK_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum((uint8_t*)temp + head, tb, lengths, out_offsets,
+                                                     (int)(n_rows + 1), s));
+    return ROGTK_OK;
+}
+
+int fill(const OpArgs& a, const int64_t* offsets, uint8_t* out_values, hipStream_t s) {
+    if (a.n > 0) hipLaunchKernelGGL(k_str_fill, dim3(grid_rows(a.n)), dim3(kBlock), 0, s, a, offsets, out_values);
+    ROGTK_HIP_CHECK(hipGetLastError());
+    return ROGTK_OK;
+}
+
+// The host entry after its checks (a: the host columns as make_args took them): the columns
+// onto the context's slots, the two passes, the result through the shared writer. Scratch:
+// out[4] the output offsets, out[5] the scan's storage, out[6] the bytes, out[7] the validity.
+int transform_host(HostCtx* c, OpArgs a, const rogtk_str_col* cols, int n_cols, rogtk_str_result* out) {
+    const int64_t n = a.n;
+    for (int k = 0; k < n_cols; ++k) {
+        DevCol d;
+        if (int rc = upload_col(c, k, HostCol(cols[k]), &d)) return rc;
+        a.cols.c[k] = as_col(d, n);
     }
-};
-thread_local std::unique_ptr<StrCtx> t_str;
+    int64_t tb = 0;
+    if (int rc = rogtk_str_temp_bytes(n, &tb)) return rc;
+    const int64_t words = std::max<int64_t>((n + 63) / 64, 1);
+    if (c->out[4].ensure((size_t)(n + 1) * 8) || c->out[5].ensure((size_t)tb) || c->out[7].ensure((size_t)words * 8))
+        return ROGTK_E_HIP;
+    const int64_t* d_off = c->out[4].as<int64_t>();
+    const uint64_t* d_valid = c->out[7].as<uint64_t>();
+    if (int rc = measure(a, c->out[4].as<int64_t>(), c->out[7].as<uint64_t>(), c->out[5].p, tb, c->stream)) return rc;
+    if (int rc = str_result_begin(c, n, d_off, d_valid, nullptr, out)) return rc;
+    // a row over the cap (a CIGAR number far beyond its sequences): an error before the
+    // output is allocated or filled
+    for (int64_t r = 0; r < n; ++r)
+        ROGTK_REQUIRE(out->offsets[r + 1] - out->offsets[r] <= ROGTK_STR_MAX_ROW_BYTES, ROGTK_E_UNSUPPORTED,
+                      "row %lld: the output is longer than ROGTK_STR_MAX_ROW_BYTES (%lld bytes)", (long long)r,
+                      (long long)ROGTK_STR_MAX_ROW_BYTES);
+    return str_result_finish(c, c->out[6], [&](uint8_t* d) { return fill(a, d_off, d, c->stream); }, out);
+}
 
 }  // namespace
 }  // namespace rogtk
@@ -177,132 +218,27 @@ int rogtk_str_measure(int op, const rogtk_str_col* cols, int n_cols, int64_t n_r
                       void* stream) {
     OpArgs a;
     if (int rc = make_args(op, cols, n_cols, n_rows, param, &a)) return rc;
-    ROGTK_REQUIRE(n_rows < (int64_t)1 << 31, ROGTK_E_UNSUPPORTED, "at most 2^31 - 1 rows per call");
-    ROGTK_REQUIRE(out_offsets && out_valid_bits && temp, ROGTK_E_INVALID, "null output / temp pointer");
-    hipStream_t s = (hipStream_t)stream;
-    int64_t* lengths = (int64_t*)temp;
-    const size_t head = ((size_t)(n_rows + 1) * 8 + 255) / 256 * 256;
-    size_t tb = 0;
-    ROGTK_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, lengths, out_offsets, (int)(n_rows + 1), s));
-    ROGTK_REQUIRE((int64_t)(head + tb) <= temp_bytes, ROGTK_E_INVALID, "temp_bytes %lld too small (need %lld)",
-                  (long long)temp_bytes, (long long)(head + tb));
-    ROGTK_HIP_CHECK(hipMemsetAsync(lengths + n_rows, 0, 8, s));
-    if (n_rows > 0)
-        hipLaunchKernelGGL(k_str_measure, dim3(grid_rows(n_rows)), dim3(kBlock), 0, s, a, lengths, out_valid_bits);
-    ROGTK_HIP_CHECK(hipGetLastError());
-    ROGTK_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum((uint8_t*)temp + head, tb, lengths, out_offsets,
-                                                     (int)(n_rows + 1), s));
-    return ROGTK_OK;
+    return measure(a, out_offsets, out_valid_bits, temp, temp_bytes, as_stream(stream));
 }
 
 int rogtk_str_fill(int op, const rogtk_str_col* cols, int n_cols, int64_t n_rows, int64_t param,
                    const int64_t* offsets, uint8_t* out_values, void* stream) {
     OpArgs a;
     if (int rc = make_args(op, cols, n_cols, n_rows, param, &a)) return rc;
-    if (n_rows > 0)
-        hipLaunchKernelGGL(k_str_fill, dim3(grid_rows(n_rows)), dim3(kBlock), 0, (hipStream_t)stream, a, offsets,
-                           out_values);
-    ROGTK_HIP_CHECK(hipGetLastError());
-    return ROGTK_OK;
+    return fill(a, offsets, out_values, as_stream(stream));
 }
 
 int rogtk_str_transform_host(int op, const rogtk_str_col* cols, int n_cols, int64_t n_rows, int64_t param,
                              rogtk_str_result* out) {
     ROGTK_REQUIRE(out && cols, ROGTK_E_INVALID, "null argument");
     *out = rogtk_str_result{};
-    {
-        OpArgs chk;
-        if (int rc = make_args(op, cols, n_cols, n_rows, param, &chk)) return rc;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        set_error("no HIP device available (librogtk_hip needs an MI355X / gfx950 GPU)");
-        return ROGTK_E_NODEVICE;
-    }
-    int dev = 0;
-    ROGTK_HIP_CHECK(hipGetDevice(&dev));
-    if (!t_str || t_str->device != dev) {
-        t_str.reset(new StrCtx());
-        t_str->device = dev;
-        ROGTK_HIP_CHECK(hipStreamCreateWithFlags(&t_str->stream, hipStreamNonBlocking));
-    }
-    StrCtx* c = t_str.get();
-    hipStream_t s = c->stream;
-    // upload the input columns (values [off(0), off(n)); offsets rebased to 0)
-    rogtk_str_col dcols[3];
-    std::vector<int64_t> off64;
-    for (int k = 0; k < n_cols; ++k) {
-        const rogtk_str_col& h = cols[k];
-        const int64_t n = h.n;
-        off64.resize(n + 1);
-        for (int64_t r = 0; r <= n; ++r)
-            off64[r] = h.offset_width == 4 ? ((const int32_t*)h.offsets)[r] : ((const int64_t*)h.offsets)[r];
-        const int64_t base = off64[0], vb = off64[n] - base;
-        ROGTK_REQUIRE(vb >= 0 && (h.values_len < 0 || off64[n] <= h.values_len), ROGTK_E_INVALID,
-                      "input %d: offsets reference bytes outside values", k);
-        for (int64_t r = 0; r <= n; ++r) off64[r] -= base;
-        if (c->off[k].ensure((size_t)(n + 1) * 8) || c->val[k].ensure((size_t)std::max<int64_t>(vb, 1)))
-            return ROGTK_E_HIP;
-        ROGTK_HIP_CHECK(hipMemcpyAsync(c->off[k].p, off64.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));
-        if (vb > 0)
-            ROGTK_HIP_CHECK(hipMemcpyAsync(c->val[k].p, h.values + base, (size_t)vb, hipMemcpyHostToDevice, s));
-        const uint8_t* dvalid = nullptr;
-        if (h.validity) {
-            const size_t nb = (size_t)((h.validity_offset + n + 7) / 8);
-            if (c->valid[k].ensure(std::max<size_t>(nb, 1))) return ROGTK_E_HIP;
-            ROGTK_HIP_CHECK(hipMemcpyAsync(c->valid[k].p, h.validity, nb, hipMemcpyHostToDevice, s));
-            dvalid = c->valid[k].as<uint8_t>();
-        }
-        // the host staging buffer is reused by the next column: wait for the copy
-        ROGTK_HIP_CHECK(hipStreamSynchronize(s));
-        dcols[k] = rogtk_str_col{c->off[k].p, 8, c->val[k].as<uint8_t>(), vb, dvalid, h.validity_offset, n};
-    }
-    int64_t tb = 0;
-    if (int rc = rogtk_str_temp_bytes(n_rows, &tb)) return rc;
-    const int64_t words = std::max<int64_t>((n_rows + 63) / 64, 1);
-    if (c->cub.ensure((size_t)tb) || c->offsets.ensure((size_t)(n_rows + 1) * 8) ||
-        c->bits.ensure((size_t)words * 8))
-        return ROGTK_E_HIP;
-    if (int rc = rogtk_str_measure(op, dcols, n_cols, n_rows, param, c->offsets.as<int64_t>(), c->bits.as<uint64_t>(),
-                                   c->cub.p, tb, s))
-        return rc;
-    int64_t* offs = (int64_t*)malloc((size_t)(n_rows + 1) * 8);
-    uint8_t* bits = (uint8_t*)malloc((size_t)words * 8);
-    if (!offs || !bits) {
-        free(offs);
-        free(bits);
-        set_error("out of host memory");
-        return ROGTK_E_INVALID;
-    }
-    *out = rogtk_str_result{n_rows, offs, nullptr, 0, bits, 0};
-    ROGTK_HIP_CHECK(hipMemcpyAsync(offs, c->offsets.p, (size_t)(n_rows + 1) * 8, hipMemcpyDeviceToHost, s));
-    ROGTK_HIP_CHECK(hipMemcpyAsync(bits, c->bits.p, (size_t)words * 8, hipMemcpyDeviceToHost, s));
-    ROGTK_HIP_CHECK(hipStreamSynchronize(s));
-    // a row over the cap (a CIGAR number far beyond its sequences): an error before the
-    // output is allocated or filled
-    for (int64_t r = 0; r < n_rows; ++r)
-        if (offs[r + 1] - offs[r] > ROGTK_STR_MAX_ROW_BYTES) {
-            rogtk_str_result_free(out);
-            set_error("row %lld: the output is longer than ROGTK_STR_MAX_ROW_BYTES (%lld bytes)", (long long)r,
-                      (long long)ROGTK_STR_MAX_ROW_BYTES);
-            return ROGTK_E_UNSUPPORTED;
-        }
-    const int64_t total = offs[n_rows];
-    out->values = (uint8_t*)malloc((size_t)std::max<int64_t>(total, 1));
-    ROGTK_REQUIRE(out->values, ROGTK_E_INVALID, "out of host memory for %lld output bytes", (long long)total);
-    out->values_len = total;
-    if (total > 0) {
-        if (c->out.ensure((size_t)total)) return ROGTK_E_HIP;
-        if (int rc = rogtk_str_fill(op, dcols, n_cols, n_rows, param, c->offsets.as<int64_t>(), c->out.as<uint8_t>(),
-                                    s))
-            return rc;
-        ROGTK_HIP_CHECK(hipMemcpyAsync(out->values, c->out.p, (size_t)total, hipMemcpyDeviceToHost, s));
-        ROGTK_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    int64_t nulls = 0;
-    for (int64_t r = 0; r < n_rows; ++r) nulls += !((bits[r >> 3] >> (r & 7)) & 1);
-    out->null_count = nulls;
-    return ROGTK_OK;
+    OpArgs a;
+    if (int rc = make_args(op, cols, n_cols, n_rows, param, &a)) return rc;
+    HostCtx* c;
+    if (int rc = host_ctx(&c)) return rc;
+    const int rc = transform_host(c, a, cols, n_cols, out);
+    if (rc) rogtk_str_result_free(out);
+    return rc;
 }
 
 void rogtk_str_result_free(rogtk_str_result* r) {
@@ -314,3 +250,4 @@ void rogtk_str_result_free(rogtk_str_result* r) {
 }
 
 }  // extern "C"
+

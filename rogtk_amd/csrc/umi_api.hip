@@ -200,7 +200,6 @@ int summary_to_host(HostCtx* c, const DevCol& col, int L, const uint32_t* did, i
     if (int rc = summary_tables(c, col, L, did, nclu, max_len, s)) return rc;
     const int64_t* rep_row = c->out[3].as<int64_t>();
     if (int rc = representatives_measure(col, rep_row, nclu, c->out[4].as<int64_t>(), c->out[5].p, tb, s)) return rc;
-    if (int rc = empty_str_result(nclu, reps)) return rc;
     for (rogtk_u32_result* r : {n_reads, n_distinct}) {
         r->n = nclu;
         r->data = (uint32_t*)calloc((size_t)std::max<int64_t>(nclu, 1), 4);
@@ -210,21 +209,13 @@ int summary_to_host(HostCtx* c, const DevCol& col, int L, const uint32_t* did, i
         if (int rc = c->d2h(n_reads->data, c->out[1].p, (size_t)nclu * 4)) return rc;
         if (int rc = c->d2h(n_distinct->data, c->out[2].p, (size_t)nclu * 4)) return rc;
     }
-    if (int rc = c->d2h(reps->offsets, c->out[4].p, (size_t)(nclu + 1) * 8)) return rc;
-    const int64_t total = reps->offsets[nclu];
-    for (int64_t k = 0; k < nclu; ++k) reps->validity[k >> 3] |= (uint8_t)(1u << (k & 7));
-    if (total > 0) {
-        free(reps->values);
-        reps->values = (uint8_t*)malloc((size_t)total);
-        ROGTK_REQUIRE(reps->values, ROGTK_E_INVALID, "out of host memory for %lld output bytes", (long long)total);
-        reps->values_len = total;
-        if (c->out[6].ensure((size_t)total)) return ROGTK_E_HIP;
-        if (int rc = representatives_fill(col.offsets, col.ow, col.values, rep_row, nclu, c->out[4].as<int64_t>(),
-                                          c->out[6].as<uint8_t>(), s))
-            return rc;
-        if (int rc = c->d2h(reps->values, c->out[6].p, (size_t)total)) return rc;
-    }
-    return ROGTK_OK;
+    if (int rc = str_result_begin(c, nclu, c->out[4].as<int64_t>(), nullptr, nullptr, reps)) return rc;
+    return str_result_finish(
+        c, c->out[6],
+        [&](uint8_t* d) {
+            return representatives_fill(col.offsets, col.ow, col.values, rep_row, nclu, c->out[4].as<int64_t>(), d, s);
+        },
+        reps);
 }
 
 int check_correct_outputs(const rogtk_str_col* col, rogtk_str_result* reps, rogtk_u32_result* n_reads,
@@ -256,20 +247,21 @@ int groups_to_host(HostCtx* c, int64_t nclu, rogtk_u32_result* cluster_group) {
 
 // The host entries' way to cluster_ids: the column (and rule.groups, here the host's keys) onto
 // the context's buffers, ids into c->out[0] (the clusters' keys into c->grp[1]) and on to
-// cluster_id. A column without rows leaves *ids empty.
+// cluster_id. A column without rows leaves *ids empty and *col without buffers.
 int host_ids(HostCtx* c, const HostCol& h, int L, ClusterRule rule, bool want_max_len, uint32_t* cluster_id,
-             ClusterIds* ids) {
+             ClusterIds* ids, DevCol* col) {
     const int64_t n = h.n;
     if (int rc = c->out[0].ensure((size_t)std::max<int64_t>(n, 4) * 4)) return rc;
     *ids = ClusterIds{c->out[0].as<uint32_t>(), nullptr, nullptr, want_max_len, 0, 0};
+    *col = DevCol(nullptr, h.ow, nullptr, nullptr, h.voff, 0);
     if (n == 0) return ROGTK_OK;
-    if (int rc = upload_col(c, h)) return rc;
+    if (int rc = upload_col(c, 0, h, col)) return rc;
     if (rule.groups) {
         if (int rc = upload_groups(c, rule.groups, n)) return rc;
         rule.groups = c->grp[0].as<uint32_t>();
         ids->cluster_group = c->grp[1].as<uint32_t>();
     }
-    if (int rc = cluster_ids(c, DevCol(c, h), L, rule, ids, c->stream)) return rc;
+    if (int rc = cluster_ids(c, *col, L, rule, ids, c->stream)) return rc;
     return c->d2h(cluster_id, ids->ids, (size_t)n * 4);
 }
 
@@ -286,7 +278,8 @@ int cluster_host(const char* name, const HostCol& h, int umi_len, const ClusterR
     HostCtx* c;
     if (int rc = host_ctx(&c)) return rc;
     ClusterIds ids;
-    if (int rc = host_ids(c, h, L, rule, false, cluster_id, &ids)) return rc;
+    DevCol dcol;
+    if (int rc = host_ids(c, h, L, rule, false, cluster_id, &ids, &dcol)) return rc;
     if (n_clusters) *n_clusters = ids.n_clusters;
     const int rc = groups_to_host(c, ids.n_clusters, cluster_group);
     if (rc) rogtk_u32_result_free(cluster_group);
@@ -316,36 +309,23 @@ int correct_host(const char* name, const rogtk_str_col* col, int umi_len, const 
     if (int rc = host_ctx(&c)) return rc;
     auto run = [&]() -> int {
         ClusterIds ids;
-        if (int rc = host_ids(c, h, L, rule, true, cluster_id, &ids)) return rc;
+        DevCol dcol;
+        if (int rc = host_ids(c, h, L, rule, true, cluster_id, &ids, &dcol)) return rc;
         const int64_t nclu = ids.n_clusters;
         if (n_clusters) *n_clusters = nclu;
         if (rule.groups)
             if (int rc = groups_to_host(c, nclu, cluster_group)) return rc;
-        const DevCol dcol(c, h);
         if (int rc = summary_to_host(c, dcol, L, ids.ids, nclu, ids.max_len, representatives, n_reads, n_distinct))
             return rc;
         // corrected: the input's offsets and nulls, every row's bytes from its representative
-        if (int rc = empty_str_result(n, corrected)) return rc;
-        for (int64_t i = 0; i <= n; ++i) corrected->offsets[i] = h.off(i);
-        for (int64_t i = 0; i < n; ++i) {
-            if (h.valid(i)) corrected->validity[i >> 3] |= (uint8_t)(1u << (i & 7));
-            else ++corrected->null_count;
-        }
-        const int64_t total = n > 0 ? h.off(n) : 0;
-        if (total > 0) {
-            free(corrected->values);
-            corrected->values = (uint8_t*)malloc((size_t)total);
-            ROGTK_REQUIRE(corrected->values, ROGTK_E_INVALID, "out of host memory for %lld output bytes",
-                          (long long)total);
-            corrected->values_len = total;
-            if (c->out[6].ensure((size_t)total)) return ROGTK_E_HIP;
-            ROGTK_HIP_CHECK(hipMemsetAsync(c->out[6].p, 0, (size_t)total, c->stream));
-            if (int rc = corrected_fill(dcol, ids.ids, nclu, c->out[3].as<int64_t>(), c->out[6].as<uint8_t>(),
-                                        c->stream))
-                return rc;
-            if (int rc = c->d2h(corrected->values, c->out[6].p, (size_t)total)) return rc;
-        }
-        return ROGTK_OK;
+        if (int rc = str_result_begin(c, n, nullptr, nullptr, &h, corrected)) return rc;
+        return str_result_finish(
+            c, c->out[6],
+            [&](uint8_t* d) -> int {
+                ROGTK_HIP_CHECK(hipMemsetAsync(d, 0, (size_t)h.off(n), c->stream));
+                return corrected_fill(dcol, ids.ids, nclu, c->out[3].as<int64_t>(), d, c->stream);
+            },
+            corrected);
     };
     const int rc = run();
     if (rc) {
@@ -468,14 +448,15 @@ int rogtk_cluster_summary_host(const rogtk_str_col* col, int umi_len, const uint
     HostCtx* c;
     if (int rc = host_ctx(&c)) return rc;
     int64_t max_len = 0;
+    DevCol dcol(nullptr, h.ow, nullptr, nullptr, h.voff, 0);
     if (n > 0) {
-        if (int rc = upload_col(c, h)) return rc;
-        if (int rc = device_max_len(c, h.ow, n, &max_len)) return rc;
+        if (int rc = upload_col(c, 0, h, &dcol)) return rc;
+        if (int rc = device_max_len(c, dcol, &max_len)) return rc;
     }
     if (int rc = c->out[0].ensure((size_t)std::max<int64_t>(n, 4) * 4)) return rc;
     if (n > 0)
         if (int rc = c->h2d(c->out[0].p, cluster_id, (size_t)n * 4)) return rc;
-    const int rc = summary_to_host(c, DevCol(c, h), L, c->out[0].as<uint32_t>(), n_clusters, max_len, representatives,
+    const int rc = summary_to_host(c, dcol, L, c->out[0].as<uint32_t>(), n_clusters, max_len, representatives,
                                    n_reads, n_distinct);
     if (rc) {
         rogtk_str_result_free(representatives);
