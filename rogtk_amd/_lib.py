@@ -10,6 +10,9 @@ import ctypes
 import os
 import threading
 
+import numpy as np
+import pyarrow as pa
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_HERE, "librogtk_hip.so")
 SYNTH_LIB_PATH = os.path.join(_HERE, "_synth", "librogtk_synth.so")
@@ -391,3 +394,59 @@ def device_count() -> int:
     n = ctypes.c_int(0)
     check(hip().rogtk_device_count(ctypes.byref(n)))
     return n.value
+
+
+# ------------------------------------------------ pointers in, library-allocated results out
+def ptr(a, null_if_empty: bool = False):
+    """A numpy array (or None) as a pointer argument; NULL for an empty one where the entry asks for that."""
+    if a is None or (null_if_empty and a.size == 0):
+        return None
+    return ctypes.c_void_p(a.ctypes.data)
+
+
+def copy_out(address, dtype, count: int) -> np.ndarray:
+    """A fresh array of count items read from a C address; empty for NULL or count <= 0."""
+    if count <= 0 or not address:
+        return np.zeros(0, dtype=dtype)
+    buf = (ctypes.c_char * (count * np.dtype(dtype).itemsize)).from_address(address)
+    return np.frombuffer(buf, dtype=dtype, count=count).copy()
+
+
+def take_str_buffers(res: StrResult):
+    """Copies of a rogtk_str_result's buffers, (n, offsets, values, validity bytes, null_count);
+    frees the result."""
+    try:
+        n = int(res.n)
+        return (n, copy_out(res.offsets, np.int64, n + 1), copy_out(res.values, np.uint8, int(res.values_len)),
+                copy_out(res.validity, np.uint8, max((n + 63) // 64 * 8, 8)), int(res.null_count))
+    finally:
+        hip().rogtk_str_result_free(ctypes.byref(res))
+
+
+def take_str(res: StrResult, typ=pa.large_string()) -> pa.Array:
+    """A rogtk_str_result as an Arrow array of its own n rows (validity only with nulls); frees the result."""
+    n, offs, vals, bits, nulls = take_str_buffers(res)
+    return pa.Array.from_buffers(typ, n, [pa.py_buffer(bits) if nulls else None, pa.py_buffer(offs),
+                                          pa.py_buffer(vals)], null_count=nulls)
+
+
+def take_u32(res: U32Result) -> pa.Array:
+    """A rogtk_u32_result as a pa.UInt32Array; frees the result."""
+    try:
+        return pa.array(copy_out(res.data, np.uint32, int(res.n)), type=pa.uint32())
+    finally:
+        hip().rogtk_u32_result_free(ctypes.byref(res))
+
+
+def take_all(results, typ=pa.large_string()) -> list:
+    """The results of one call as Arrow arrays. Every one is taken, and so freed, before the
+    first failure of a conversion is raised."""
+    out, failure = [], None
+    for r in results:
+        try:
+            out.append(take_str(r, typ) if isinstance(r, StrResult) else take_u32(r))
+        except BaseException as e:  # noqa: B036 - raised below, once nothing is left to free
+            failure = failure or e
+    if failure is not None:
+        raise failure
+    return out

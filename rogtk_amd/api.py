@@ -33,13 +33,13 @@ All computation runs in librogtk_hip.so on the GPU; errors are RogtkError.
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Union
+from typing import Union
 
 import numpy as np
 import pyarrow as pa
 
 from . import _lib
-from .columns import ColumnLike, _one_chunk, chunks, concat, validity_buffer
+from .columns import ColumnLike, as_u32, chunks, concat, one_chunk, validity_buffer
 
 FIELDS = (
     ("shannon_entropy", pa.float64()),
@@ -52,10 +52,6 @@ FIELDS = (
 )
 _FIELD_NAMES = tuple(f for f, _ in FIELDS)
 STRUCT_TYPE = pa.struct([pa.field(n, t) for n, t in FIELDS])
-
-
-def _ptr(a: Optional[np.ndarray]):
-    return None if a is None else ctypes.c_void_p(a.ctypes.data)
 
 
 class _PinnedBlock:
@@ -90,10 +86,8 @@ def _complexity_chunk(ch, want: tuple):
     for name, typ in FIELDS:
         if name in want:
             out[name] = _out(n, np.uint32 if name == "longest_homopolymer_run" else np.float64)
-    sc = _lib.UmiScores(*[_ptr(out.get(name)) for name in _FIELD_NAMES])
-    o, v, val = ch.ptrs()
-    _lib.call("rogtk_umi_complexity_host", o, ch.offset_width, v, ch.values.size, val,
-              ch.validity_offset, n, ctypes.byref(sc))
+    sc = _lib.UmiScores(*[_lib.ptr(out.get(name)) for name in _FIELD_NAMES])
+    _lib.call("rogtk_umi_complexity_host", *ch.loose(), ctypes.byref(sc))
     return {k: a[:n] for k, a in out.items()}
 
 
@@ -150,9 +144,7 @@ def _hamming(column, target, max_distance, want_dist):
         n = ch.n
         dist = _out(n, np.uint32) if want_dist else None
         bits = None if want_dist else _out((n + 7) // 8, np.uint8)
-        o, v, val = ch.ptrs()
-        _lib.call("rogtk_hamming_host", o, ch.offset_width, v, ch.values.size, val, ch.validity_offset,
-                  n, _ptr(tb), len(t), maxd, _ptr(dist), _ptr(bits))
+        _lib.call("rogtk_hamming_host", *ch.loose(), _lib.ptr(tb), len(t), maxd, _lib.ptr(dist), _lib.ptr(bits))
         vbuf = validity_buffer(ch)
         if want_dist:
             arrays.append(pa.Array.from_buffers(pa.uint32(), n, [vbuf, pa.py_buffer(dist)]))
@@ -174,28 +166,6 @@ def umi_method_entry(method: str, max_distance: int, cluster_entry: str, directi
     if int(max_distance) not in (0, 1):
         raise _lib.RogtkError(_lib.ROGTK_E_UNSUPPORTED, f"max_distance {max_distance}: only 0 and 1 are supported")
     return directional_entry
-
-
-def group_keys(groups, n: int) -> np.ndarray:
-    """The ``groups`` argument of the grouped calls as n contiguous uint32 keys:
-    a numpy or Arrow integer array (or chunked array) of the column's length, values in
-    0..2^32-1, no nulls. Anything else is a ValueError, before the library is called."""
-    if isinstance(groups, pa.ChunkedArray):
-        groups = groups.combine_chunks() if groups.num_chunks else pa.array([], type=groups.type)
-    if isinstance(groups, pa.Array):
-        if not pa.types.is_integer(groups.type):
-            raise ValueError(f"groups must be an integer array, got {groups.type}")
-        if groups.null_count:
-            raise ValueError(f"groups has {groups.null_count} null keys; every row needs a key")
-        groups = groups.to_numpy(zero_copy_only=False)
-    g = np.asarray(groups)
-    if g.dtype.kind not in "iu":
-        raise ValueError(f"groups must be an integer array, got dtype {g.dtype}")
-    if g.shape != (n,):
-        raise ValueError(f"groups has shape {g.shape}, the column has {n} rows")
-    if g.size and (int(g.min()) < 0 or int(g.max()) > 0xFFFFFFFF):
-        raise ValueError("groups must hold values in 0..2^32-1")
-    return np.ascontiguousarray(g, dtype=np.uint32)
 
 
 def grouped_method(method: str, max_distance: int) -> int:
@@ -226,19 +196,17 @@ def umi_cluster(column: ColumnLike, umi_len: int = 0, max_distance: int = 1, met
         entry, m = "rogtk_umi_cluster_grouped_host", grouped_method(method, max_distance)
     else:
         entry = umi_method_entry(method, max_distance, "rogtk_umi_cluster_host", "rogtk_umi_cluster_directional_host")
-    ch = _one_chunk(column)
+    ch = one_chunk(column)
     n = ch.n
     cid = _out(n, np.uint32)
     nclu, rl = ctypes.c_int64(0), ctypes.c_int(0)
     rule = [int(umi_len), int(max_distance)]
     tail = []
     if groups is not None:  # the keys before the rule, the method in it; the clusters' keys are not asked for
-        keys = group_keys(groups, n)
-        rule = [_ptr(keys) if n else None, rule[0], m, rule[1]]
+        keys = as_u32(groups, "groups", rows=n)
+        rule = [_lib.ptr(keys, null_if_empty=True), rule[0], m, rule[1]]
         tail = [None]
-    o, v, val = ch.ptrs()
-    _lib.call(entry, o, ch.offset_width, v, ch.values.size, val, ch.validity_offset, n, *rule, _ptr(cid),
-              ctypes.byref(nclu), ctypes.byref(rl), *tail)
+    _lib.call(entry, *ch.loose(), *rule, _lib.ptr(cid), ctypes.byref(nclu), ctypes.byref(rl), *tail)
     out = pa.Array.from_buffers(pa.uint32(), n, [validity_buffer(ch), pa.py_buffer(cid)])
     return out, int(nclu.value), int(rl.value)
 
@@ -255,11 +223,10 @@ def kmer_spectrum(column: ColumnLike, k: int, min_coverage: int, auto_k: bool = 
     kmer_hi / kmer_lo (u64; hi only for k_eff 64), exts (u8), counts (u16),
     entry_offsets (n_groups + 1) and stats (n_groups x 5, columns KMER_STATS).
     """
-    ch = _one_chunk(column)
+    ch = one_chunk(column)
     n = ch.n
-    o, v, val = ch.ptrs()
     cap = ctypes.c_int64(0)
-    _lib.call("rogtk_kmer_capacity", o, ch.offset_width, n, ctypes.byref(cap))
+    _lib.call("rogtk_kmer_capacity", _lib.ptr(ch.offsets), ch.offset_width, n, ctypes.byref(cap))
     capn = max(int(cap.value), 1)
     go = None if group_offsets is None else np.ascontiguousarray(group_offsets, dtype=np.int64)
     G = 1 if go is None else len(go) - 1
@@ -268,9 +235,8 @@ def kmer_spectrum(column: ColumnLike, k: int, min_coverage: int, auto_k: bool = 
     cn = np.empty(capn, dtype=np.uint16)
     eo = np.empty(G + 1, dtype=np.int64)
     st = np.empty(5 * G, dtype=np.int64)
-    _lib.call("rogtk_kmer_spectrum_host", o, ch.offset_width, v, ch.values.size, val, ch.validity_offset, n,
-              _ptr(go), 0 if go is None else G, int(k), int(bool(auto_k)), int(min_coverage), capn,
-              _ptr(km), _ptr(ex), _ptr(cn), _ptr(eo), _ptr(st))
+    _lib.call("rogtk_kmer_spectrum_host", *ch.loose(), _lib.ptr(go), 0 if go is None else G, int(k), int(bool(auto_k)),
+              int(min_coverage), capn, _lib.ptr(km), _lib.ptr(ex), _lib.ptr(cn), _lib.ptr(eo), _lib.ptr(st))
     m = int(eo[G])
     return {"kmer_hi": km[0:2 * m:2].copy(), "kmer_lo": km[1:2 * m:2].copy(), "exts": ex[:m].copy(),
             "counts": cn[:m].copy(), "entry_offsets": eo, "stats": st.reshape(G, 5)}

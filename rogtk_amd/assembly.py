@@ -27,16 +27,7 @@ import numpy as np
 import pyarrow as pa
 
 from . import _lib
-from .columns import ColumnLike, chunks
-
-
-def _group(column: ColumnLike):
-    arr = column
-    if isinstance(arr, pa.ChunkedArray):
-        arr = arr.combine_chunks() if arr.num_chunks else pa.array([], type=arr.type)
-    chs = list(chunks(arr))
-    assert len(chs) == 1
-    return chs[0]
+from .columns import ColumnLike, one_chunk
 
 
 def _enc(s: Optional[str]):
@@ -44,18 +35,17 @@ def _enc(s: Optional[str]):
 
 
 def _assemble(column, k, min_coverage, method, start_anchor, end_anchor, min_length, only_largest, auto_k) -> str:
-    ch = _group(column)
-    o, v, val = ch.ptrs()
+    ch = one_chunk(column)
     need = ctypes.c_int64(0)
     nc = ctypes.c_int64(0)
     cap = max(int(ch.values.size) * 2 + 1024, 4096)
     while True:
         buf = ctypes.create_string_buffer(cap)
         try:
-            _lib.call("rogtk_assemble_host", o, ch.offset_width, v, ch.values.size, val, ch.validity_offset, ch.n,
-                      int(k), int(min_coverage), _enc(method), _enc(start_anchor), _enc(end_anchor),
-                      int(bool(only_largest)), -1 if min_length is None else int(min_length), int(bool(auto_k)),
-                      buf, cap, ctypes.byref(need), ctypes.byref(nc))
+            _lib.call("rogtk_assemble_host", *ch.loose(), int(k), int(min_coverage), _enc(method),
+                      _enc(start_anchor), _enc(end_anchor), int(bool(only_largest)),
+                      -1 if min_length is None else int(min_length), int(bool(auto_k)), buf, cap, ctypes.byref(need),
+                      ctypes.byref(nc))
         except _lib.RogtkError as e:
             if e.code == _lib.ROGTK_E_OVERFLOW and need.value > cap:
                 cap = int(need.value)
@@ -108,17 +98,16 @@ def sweep_assembly_params(column: ColumnLike, k_start: int = 5, k_end: int = 32,
                           prefix: Optional[str] = None, auto_k: bool = False) -> pa.StructArray:
     """sweep_assembly_params_expr: one row per (k, min_coverage) of the grid, largest
     contig length (0 when none). The k-mer spectrum is computed once per effective k."""
-    ch = _group(column)
-    o, v, val = ch.ptrs()
+    ch = one_chunk(column)
     nk = max(0, (k_end - k_start) // k_step + 1) if k_step > 0 and k_end >= k_start else 0
     nc = max(0, (cov_end - cov_start) // cov_step + 1) if cov_step > 0 and cov_end >= cov_start else 0
     cap = max(nk * nc, 1)
     ok, oc, ol = (np.zeros(cap, dtype=np.int64) for _ in range(3))
     n = ctypes.c_int64(0)
-    p = lambda a: ctypes.c_void_p(a.ctypes.data)
-    _lib.call("rogtk_assembly_sweep_host", o, ch.offset_width, v, ch.values.size, val, ch.validity_offset, ch.n,
-              int(k_start), int(k_end), int(k_step), int(cov_start), int(cov_end), int(cov_step), _enc(method),
-              _enc(start_anchor), _enc(end_anchor), cap, p(ok), p(oc), p(ol), ctypes.byref(n))
+    p = _lib.ptr
+    _lib.call("rogtk_assembly_sweep_host", *ch.loose(), int(k_start), int(k_end), int(k_step), int(cov_start),
+              int(cov_end), int(cov_step), _enc(method), _enc(start_anchor), _enc(end_anchor), cap, p(ok), p(oc), p(ol),
+              ctypes.byref(n))
     m = int(n.value)
     return pa.StructArray.from_arrays([pa.array(ok[:m]), pa.array(oc[:m]), pa.array(ol[:m])],
                                       fields=list(SWEEP_TYPE))
@@ -132,16 +121,15 @@ def optimize_assembly(column: ColumnLike, method: str = "shortest_path", start_a
     """optimize_assembly_expr (fracture_opt.rs:283-356): greedy beam over (k, min_coverage)."""
     if start_anchor is None or end_anchor is None:
         raise ValueError("Both start_anchor and end_anchor are required")
-    ch = _group(column)
-    o, v, val = ch.ptrs()
-    out4 = (ctypes.c_uint32 * 4)()
+    ch = one_chunk(column)
+    out4 =(ctypes.c_uint32 * 4)()
     need = ctypes.c_int64(0)
     cap = max(int(ch.values.size) * 2 + 1024, 4096)
     while True:
         buf = ctypes.create_string_buffer(cap)
         try:
-            _lib.call("rogtk_assembly_optimize_host", o, ch.offset_width, v, ch.values.size, val, ch.validity_offset,
-                      ch.n, _enc(method), _enc(start_anchor), _enc(end_anchor), int(start_k), int(start_min_coverage),
+            _lib.call("rogtk_assembly_optimize_host", *ch.loose(), _enc(method), _enc(start_anchor),
+                      _enc(end_anchor), int(start_k), int(start_min_coverage),
                       50 if max_iterations is None else int(max_iterations), int(bool(explore_k)),
                       int(bool(prioritize_length)), buf, cap, ctypes.byref(need), out4)
         except _lib.RogtkError as e:
@@ -174,7 +162,7 @@ def assemble_groups(spectrum: dict, method: str = "compression", start_anchor: O
     eo = host(spectrum["entry_offsets"], np.int64)
     st = host(spectrum["stats"], np.int64).reshape(-1)
     G = len(eo) - 1
-    p = lambda a: ctypes.c_void_p(a.ctypes.data) if a.size else None
+    p = lambda a: _lib.ptr(a, null_if_empty=True)
     h = ctypes.c_void_p()
     _lib.call("rogtk_assemble_groups_host", p(km), p(ex), p(cn), p(eo), p(st), G, _enc(method), _enc(start_anchor),
               _enc(end_anchor), int(bool(only_largest)), -1 if min_length is None else int(min_length),

@@ -61,17 +61,10 @@ def bam_schema(include_sequence: bool = True, include_quality: bool = True,
     return pa.schema(fields)
 
 
-def _np_from(ptr: int, dtype, count: int) -> np.ndarray:
-    if count <= 0 or not ptr:
-        return np.zeros(0, dtype=dtype)
-    buf = (ctypes.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr)
-    return np.frombuffer(buf, dtype=dtype, count=count).copy()
-
-
 def _validity(ptr: int, n: int):
     if not ptr or n == 0:
         return None, 0
-    bits = _np_from(ptr, np.uint8, (n + 7) // 8)
+    bits = _lib.copy_out(ptr, np.uint8, (n + 7) // 8)
     nulls = n - int(np.unpackbits(bits, bitorder="little")[:n].sum())
     return (pa.py_buffer(bits), nulls) if nulls else (None, 0)
 
@@ -153,8 +146,8 @@ class BamReader:
         tl = ctypes.c_int64()
         _lib.call("rogtk_bam_header", self._h, ctypes.byref(n), ctypes.byref(off), ctypes.byref(val),
                   ctypes.byref(txt), ctypes.byref(tl))
-        o = _np_from(off.value, np.int64, n.value + 1)
-        v = _np_from(val.value, np.uint8, int(o[-1]) if len(o) else 0).tobytes()
+        o = _lib.copy_out(off.value, np.int64, n.value + 1)
+        v = _lib.copy_out(val.value, np.uint8, int(o[-1]) if len(o) else 0).tobytes()
         return [v[o[i]:o[i + 1]].decode() for i in range(n.value)]
 
     def next_batch(self, max_records: int, mode: str = "noodles", include_sequence: bool = True,
@@ -170,8 +163,8 @@ class BamReader:
         cols = []
 
         def string_col(c):
-            off = _np_from(b.offsets[c], np.int64, n + 1)
-            vals = _np_from(b.values[c], np.uint8, int(off[-1]))
+            off = _lib.copy_out(b.offsets[c], np.int64, n + 1)
+            vals = _lib.copy_out(b.values[c], np.uint8, int(off[-1]))
             vbuf, nulls = _validity(b.validity[c], n)
             if off[-1] < 2 ** 31:
                 return pa.Array.from_buffers(pa.string(), n, [vbuf, pa.py_buffer(off.astype(np.int32)),
@@ -181,7 +174,7 @@ class BamReader:
             return arr.cast(pa.string())
 
         def u32_col(c):
-            vals = _np_from(b.u32[c], np.uint32, n)
+            vals = _lib.copy_out(b.u32[c], np.uint32, n)
             vbuf, nulls = _validity(b.u32_validity[c], n)
             return pa.Array.from_buffers(pa.uint32(), n, [vbuf, pa.py_buffer(vals)], null_count=nulls)
 

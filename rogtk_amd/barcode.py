@@ -27,8 +27,7 @@ import numpy as np
 import pyarrow as pa
 
 from . import _lib
-from .columns import ColumnLike
-from .correct import _desc, _one_chunk, _take_str, _text_type
+from .columns import ColumnLike, as_u32, one_chunk, text_type
 
 STATUS = ("exact", "corrected", "ambiguous", "no_match", "null")
 AMBIGUOUS = ("counts", "reject")
@@ -95,34 +94,17 @@ def _ambiguous(ambiguous: str) -> int:
     return AMBIGUOUS.index(ambiguous)
 
 
-def _u32_counts(counts, W: int, name: str) -> np.ndarray:
-    if isinstance(counts, pa.ChunkedArray):
-        counts = counts.combine_chunks() if counts.num_chunks else pa.array([], type=counts.type)
-    if isinstance(counts, pa.Array):
-        if counts.null_count:
-            raise ValueError(f"{name} has nulls")
-        counts = counts.to_numpy(zero_copy_only=False)
-    c = np.asarray(counts)
-    if c.dtype.kind not in "iu":
-        raise ValueError(f"{name} must be an integer array, got dtype {c.dtype}")
-    if c.shape != (W,):
-        raise ValueError(f"{name} has shape {c.shape}, the whitelist has {W} entries")
-    if c.size and (int(c.min()) < 0 or int(c.max()) > 0xFFFFFFFF):
-        raise ValueError(f"{name} must hold values in 0..2^32-1")
-    return np.ascontiguousarray(c, dtype=np.uint32)
-
-
 class BarcodeWhitelist:
     """The device handle of a whitelist: immutable, bound to the device current at creation,
     reusable across calls and batches. whitelist: Arrow, numpy or a list of str / bytes; its
     row number is the barcode's index."""
 
     def __init__(self, whitelist: ColumnLike):
-        ch = _one_chunk(whitelist)
+        ch = one_chunk(whitelist)
         self.barcode_len = validate_whitelist(ch)
         self.size = ch.n
         self._h = ctypes.c_void_p(None)
-        desc = _desc(ch)
+        desc = ch.desc()
         _lib.check(_lib.hip().rogtk_barcode_whitelist_create(ctypes.byref(desc), ctypes.byref(self._h)))
 
     def __del__(self):
@@ -154,24 +136,18 @@ class BarcodeWhitelist:
         counts (u32 [W], optional): the prior counts under ambiguous="counts"; default: the
         exact rows of this call."""
         amb = _ambiguous(ambiguous)
-        prior = None if counts is None else _u32_counts(counts, self.size, "counts")
-        ch = _one_chunk(column)
+        prior = None if counts is None else as_u32(counts, "counts", rows=self.size)
+        ch = one_chunk(column)
         n, W = ch.n, self.size
         index = np.zeros(max(n, 1), dtype=np.uint32)
         status = np.zeros(max(n, 1), dtype=np.uint8)
         exact, final = np.zeros(W, dtype=np.uint32), np.zeros(W, dtype=np.uint32)
         totals = (ctypes.c_int64 * 5)()
         corrected = _lib.StrResult()
-        desc = _desc(ch)
-        lib = _lib.hip()
-        p = lambda a: ctypes.c_void_p(a.ctypes.data)
-        _lib.check(lib.rogtk_barcode_correct_host(self._h, ctypes.byref(desc), amb, None if prior is None else p(prior),
-                                                  p(index), p(status), ctypes.byref(corrected), p(exact), p(final),
-                                                  totals))
-        try:
-            out = _take_str(corrected, _text_type(ch))
-        finally:
-            lib.rogtk_str_result_free(ctypes.byref(corrected))
+        desc, p = ch.desc(), _lib.ptr
+        _lib.call("rogtk_barcode_correct_host", self._h, ctypes.byref(desc), amb, p(prior), p(index), p(status),
+                  ctypes.byref(corrected), p(exact), p(final), totals)
+        out = _lib.take_str(corrected, text_type(ch))
         index, status = index[:n], status[:n]
         idx = pa.array(index, type=pa.uint32(), mask=status > 1) if n else pa.array([], type=pa.uint32())
         return BarcodeCorrection(idx, status, out, exact, final, {k: int(totals[i]) for i, k in enumerate(STATUS)})
@@ -208,10 +184,8 @@ class BarcodeWhitelist:
         elif not (isinstance(into, np.ndarray) and into.dtype == np.uint32 and into.shape == (self.size,)
                   and into.flags.c_contiguous and into.flags.writeable):
             raise ValueError(f"into must be a writable contiguous uint32 array of {self.size} entries")
-        ch = _one_chunk(column)
-        desc = _desc(ch)
-        _lib.check(_lib.hip().rogtk_barcode_count_host(self._h, ctypes.byref(desc), ctypes.c_void_p(into.ctypes.data),
-                                                       None))
+        desc = one_chunk(column).desc()
+        _lib.call("rogtk_barcode_count_host", self._h, ctypes.byref(desc), _lib.ptr(into), None)
         return into
 
 

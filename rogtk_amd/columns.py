@@ -1,26 +1,29 @@
-"""Arrow string columns as the C ABI sees them (offsets, values, validity).
+"""What a Python wrapper hands to the C ABI: Arrow string columns as host buffers (offsets,
+values, validity) and per-row integer arguments as uint32 arrays.
 
 The reference receives polars String series (possibly multi-chunk) through the
 polars plugin ABI (src/expressions.rs:1236 `inputs[0].str()?`). Here a column is
 any of: pyarrow (Large)StringArray / ChunkedArray, a Python sequence of
 str/bytes/None, or a numpy fixed-width bytes array ('S<L>'). Each chunk is handed
-to librogtk_hip as plain host buffers with offsets rebased to 0.
+to librogtk_hip as plain host buffers, with offsets rebased to 0 for the entries that ask
+for that and as Arrow holds them for the entries whose upload rebases.
 """
 from __future__ import annotations
 
-import ctypes
 from dataclasses import dataclass
 from typing import Iterator, Optional, Sequence, Union
 
 import numpy as np
 import pyarrow as pa
 
+from . import _lib
+
 ColumnLike = Union[pa.Array, pa.ChunkedArray, Sequence[Optional[Union[str, bytes]]], np.ndarray]
 
 
 @dataclass
 class HostChunk:
-    """One Arrow string chunk as contiguous host buffers (offsets start at 0)."""
+    """One Arrow string chunk as contiguous host buffers. The numpy views keep Arrow's memory."""
 
     offsets: np.ndarray           # int32 or int64, n+1
     values: np.ndarray            # uint8
@@ -33,9 +36,22 @@ class HostChunk:
     def offset_width(self) -> int:
         return self.offsets.dtype.itemsize
 
-    def ptrs(self):
-        vp = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
-        return vp(self.offsets), vp(self.values), vp(self.validity)
+    def loose(self) -> tuple:
+        """The column as the seven arguments of the entries that take it loose."""
+        return (_lib.ptr(self.offsets), self.offset_width, _lib.ptr(self.values), self.values.size,
+                _lib.ptr(self.validity), self.validity_offset, self.n)
+
+    def desc(self) -> _lib.StrCol:
+        """The column as a rogtk_str_col. It holds raw addresses, so it carries the chunk."""
+        d = _lib.StrCol(*self.loose())
+        d.chunk = self
+        return d
+
+
+def text_type(ch: HostChunk):
+    """The Arrow type of a string output of the chunk: binary in, binary out."""
+    t = ch.arrow.type
+    return pa.large_binary() if pa.types.is_binary(t) or pa.types.is_large_binary(t) else pa.large_string()
 
 
 def _to_arrow(col: ColumnLike) -> Union[pa.Array, pa.ChunkedArray]:
@@ -67,36 +83,71 @@ def chunks(col: ColumnLike) -> Iterator[HostChunk]:
         yield _chunk(a)
 
 
-def _one_chunk(col: ColumnLike) -> HostChunk:
+def one_chunk(col: ColumnLike, rebase: bool = True) -> HostChunk:
     """The column as one batch: what a call whose answer is global to the column takes."""
     arr = _to_arrow(col)
     if isinstance(arr, pa.ChunkedArray):
-        arr = arr.combine_chunks() if arr.num_chunks else pa.array([], type=arr.type)
-    chs = list(chunks(arr))
-    assert len(chs) == 1
-    return chs[0]
+        if arr.num_chunks == 1:
+            arr = arr.chunk(0)
+        else:
+            arr = arr.combine_chunks() if arr.num_chunks else pa.array([], type=arr.type)
+    return _chunk(arr, rebase)
 
 
-def _chunk(a: pa.Array) -> HostChunk:
+def _chunk(a: pa.Array, rebase: bool = True) -> HostChunk:
+    """rebase: offsets from 0 over the chunk's own bytes (a copy of the offsets for a slice). Not
+    rebase: Arrow's offsets from a.offset on and the whole values buffer, for the entries whose
+    upload rebases; no pass over the offsets."""
     n = len(a)
-    bufs = a.buffers()
-    validity_buf, offsets_buf, values_buf = bufs[0], bufs[1], bufs[2]
+    validity_buf, offsets_buf, values_buf = a.buffers()[:3]
     wide = pa.types.is_large_string(a.type) or pa.types.is_large_binary(a.type)
     odt = np.int64 if wide else np.int32
-    offs = np.frombuffer(offsets_buf, dtype=odt, count=a.offset + n + 1)[a.offset:]
-    base = int(offs[0]) if n + 1 > 0 else 0
-    end = int(offs[-1])
-    if values_buf is not None and end > base:
-        values = np.frombuffer(values_buf, dtype=np.uint8, count=end)[base:end]
+    if offsets_buf is not None:
+        offs = np.frombuffer(offsets_buf, dtype=odt, count=a.offset + n + 1)[a.offset:]
     else:
-        values = np.zeros(1, dtype=np.uint8)
-    offs = np.ascontiguousarray(offs - base, dtype=odt) if base else np.ascontiguousarray(offs)
+        offs = np.zeros(n + 1, dtype=odt)
+    values = np.zeros(1, dtype=np.uint8)
+    if not rebase:
+        if values_buf is not None and values_buf.size:
+            values = np.frombuffer(values_buf, dtype=np.uint8)
+    else:
+        base, end = int(offs[0]), int(offs[-1])
+        if values_buf is not None and end > base:
+            values = np.frombuffer(values_buf, dtype=np.uint8, count=end)[base:end]
+        if base:
+            offs = np.ascontiguousarray(offs - base, dtype=odt)
     validity = None
     voff = 0
     if a.null_count > 0 and validity_buf is not None:
         validity = np.frombuffer(validity_buf, dtype=np.uint8)
         voff = a.offset
-    return HostChunk(offs, np.ascontiguousarray(values), validity, voff, n, a)
+    return HostChunk(offs, values, validity, voff, n, a)
+
+
+def as_u32(x, name: str, *, rows: Optional[int] = None, nulls_to: Optional[int] = None) -> np.ndarray:
+    """A per-row integer argument (numpy, Arrow or chunked Arrow) as a contiguous uint32 array,
+    x's own memory when it already is one. Anything that is not `rows` integers in 0..2^32-1 is
+    a ValueError, in this order: type, nulls (filled with nulls_to when given), shape, range."""
+    if isinstance(x, pa.ChunkedArray):
+        x = x.combine_chunks() if x.num_chunks else pa.array([], type=x.type)
+    if isinstance(x, pa.Array):
+        if not pa.types.is_integer(x.type):
+            raise ValueError(f"{name} must be an integer array, got {x.type}")
+        if x.null_count:
+            if nulls_to is None:
+                raise ValueError(f"{name} has {x.null_count} nulls")
+            x = (x if pa.types.is_uint64(x.type) else x.cast(pa.int64())).fill_null(nulls_to)
+        x = x.to_numpy(zero_copy_only=False)
+    a = np.asarray(x)
+    if a.dtype.kind not in "iu" and (a.size or isinstance(x, np.ndarray)):  # a sequence without items has no type
+        raise ValueError(f"{name} must be an integer array, got dtype {a.dtype}")
+    if a.ndim != 1:
+        raise ValueError(f"{name} must be 1-D, got shape {a.shape}")
+    if rows is not None and a.size != rows:
+        raise ValueError(f"{name} has shape {a.shape}, expected ({rows},)")
+    if a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+        raise ValueError(f"{name} must hold values in 0..2^32-1")
+    return np.ascontiguousarray(a, dtype=np.uint32)
 
 
 def validity_buffer(chunk: HostChunk) -> Optional[pa.Buffer]:

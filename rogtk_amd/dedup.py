@@ -25,6 +25,7 @@ import numpy as np
 import pyarrow as pa
 
 from . import _lib
+from .columns import as_u32
 
 NO_ID = 0xFFFFFFFF
 BEST_FIELDS = ("best_row", "best_score", "n_reads")
@@ -53,32 +54,6 @@ def _is_tensor(x) -> bool:
     return type(x).__module__.split(".")[0] == "torch"
 
 
-def _host_u32(x, name: str, nulls_to: Optional[int]) -> np.ndarray:
-    """x as a 1-D contiguous uint32 array; a ValueError for anything that is not one exactly."""
-    if isinstance(x, pa.ChunkedArray):
-        x = x.combine_chunks() if x.num_chunks else pa.array([], type=x.type)
-    if isinstance(x, pa.Array):
-        if not pa.types.is_integer(x.type):
-            raise ValueError(f"{name} must be an integer array, got {x.type}")
-        if x.null_count:
-            if nulls_to is None:
-                raise ValueError(f"{name} has {x.null_count} nulls")
-            x = x.cast(pa.int64()).fill_null(nulls_to) if not pa.types.is_uint64(x.type) else x.fill_null(nulls_to)
-        x = x.to_numpy(zero_copy_only=False)
-    a = np.asarray(x)
-    if a.ndim != 1:
-        raise ValueError(f"{name} must be 1-D, got shape {a.shape}")
-    if a.dtype.kind not in "iu":
-        raise ValueError(f"{name} must be an integer array, got dtype {a.dtype}")
-    if a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
-        raise ValueError(f"{name} must hold values in 0..2^32-1")
-    return np.ascontiguousarray(a, dtype=np.uint32)
-
-
-def _ptr(a: Optional[np.ndarray]):
-    return None if a is None or a.size == 0 else ctypes.c_void_p(a.ctypes.data)
-
-
 def _best_rows_host(cid: np.ndarray, sc: Optional[np.ndarray], k: int) -> DedupResult:
     n = cid.size
     if not 0 <= k < NO_ID:
@@ -89,8 +64,9 @@ def _best_rows_host(cid: np.ndarray, sc: Optional[np.ndarray], k: int) -> DedupR
     words = np.empty((n + 63) // 64, np.uint64)
     kept = np.empty(min(n, k), np.int64)
     n_kept = ctypes.c_int64(0)
-    _lib.call("rogtk_cluster_best_rows_host", _ptr(cid), _ptr(sc), n, k, _ptr(best_row), _ptr(best_score),
-              _ptr(n_reads), _ptr(words), _ptr(kept), ctypes.byref(n_kept))
+    p = lambda a: _lib.ptr(a, null_if_empty=True)
+    _lib.call("rogtk_cluster_best_rows_host", p(cid), p(sc), n, k, p(best_row), p(best_score), p(n_reads), p(words),
+              p(kept), ctypes.byref(n_kept))
     keep = pa.Array.from_buffers(pa.bool_(), n, [None, pa.py_buffer(words)], null_count=0)
     best = pa.StructArray.from_arrays(
         [pa.array(best_row, type=pa.int64()), pa.array(best_score, type=pa.uint32()),
@@ -150,12 +126,8 @@ def cluster_best_rows(cluster_id, score=None, n_clusters: int = -1) -> DedupResu
     tensors give torch tensors out (keep as int64 bitmap words, best as a dict of tensors)."""
     if _is_tensor(cluster_id):
         return _best_rows_device(cluster_id, score, int(n_clusters))
-    cid = _host_u32(cluster_id, "cluster_id", NO_ID)
-    sc = None
-    if score is not None:
-        sc = _host_u32(score, "score", None)
-        if sc.shape != cid.shape:
-            raise ValueError(f"score has shape {sc.shape}, cluster_id has {cid.size} rows")
+    cid = as_u32(cluster_id, "cluster_id", nulls_to=NO_ID)
+    sc = None if score is None else as_u32(score, "score", rows=cid.size)
     k = int(n_clusters)
     if k < 0:
         real = cid[cid != NO_ID]
@@ -169,9 +141,7 @@ def umi_dedup(column, umi_len: int = 0, score=None, max_distance: int = 1, metho
     every method / groups rule and refusal is that call's. Null UMI rows are never kept."""
     from .api import umi_cluster
 
-    sc = None if score is None else _host_u32(score, "score", None)
-    if sc is not None and sc.size != len(column):
-        raise ValueError(f"score has shape {sc.shape}, the column has {len(column)} rows")
+    sc = None if score is None else as_u32(score, "score", rows=len(column))
     ids, k, rl = umi_cluster(column, umi_len, max_distance, method, groups)
     res = cluster_best_rows(ids, sc, k)
     res.cluster_id, res.n_clusters, res.umi_len = ids, k, rl

@@ -23,9 +23,9 @@ SCHEMA = pa.schema([pa.field(c, pa.string(), nullable=False) for c in COLUMNS])
 
 
 def _array(off_ptr, val_ptr, n: int) -> pa.Array:
-    offs = np.ctypeslib.as_array(ctypes.cast(off_ptr, ctypes.POINTER(ctypes.c_int64)), shape=(n + 1,)).copy()
+    offs = _lib.copy_out(off_ptr, np.int64, n + 1)
     nbytes = int(offs[-1])
-    vals = ctypes.string_at(val_ptr, nbytes) if nbytes else b""
+    vals = _lib.copy_out(val_ptr, np.uint8, nbytes)
     if nbytes < 2 ** 31 - 1:
         return pa.Array.from_buffers(pa.string(), n, [None, pa.py_buffer(offs.astype(np.int32)), pa.py_buffer(vals)])
     return pa.Array.from_buffers(pa.large_string(), n, [None, pa.py_buffer(offs), pa.py_buffer(vals)])

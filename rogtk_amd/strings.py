@@ -23,82 +23,45 @@ import numpy as np
 import pyarrow as pa
 
 from . import _lib
-from .columns import ColumnLike, _to_arrow
+from .columns import ColumnLike, one_chunk
 
 REVCOMP, PARSE_CIGAR, ALIGNED_REF, ALIGNED_QUERY, CIGAR_INSERTIONS, ENRICH_ALLELE, PHRED_STR, PHRED_LIST = range(1, 9)
 
 
-def _single(col: ColumnLike) -> pa.Array:
-    a = _to_arrow(col)
-    if isinstance(a, pa.ChunkedArray):
-        a = a.combine_chunks() if a.num_chunks != 1 else a.chunk(0)
-    return a
-
-
-def _desc(a: pa.Array, keep: list) -> _lib.StrCol:
-    bufs = a.buffers()
-    wide = pa.types.is_large_string(a.type) or pa.types.is_large_binary(a.type)
-    odt = np.int64 if wide else np.int32
-    n = len(a)
-    offs = np.frombuffer(bufs[1], dtype=odt, count=a.offset + n + 1)[a.offset:] if bufs[1] is not None \
-        else np.zeros(n + 1, dtype=odt)
-    offs = np.ascontiguousarray(offs)
-    vals = np.frombuffer(bufs[2], dtype=np.uint8) if bufs[2] is not None and bufs[2].size else np.zeros(1, np.uint8)
-    valid = np.frombuffer(bufs[0], dtype=np.uint8) if a.null_count > 0 and bufs[0] is not None else None
-    keep.extend([offs, vals, valid])
-    return _lib.StrCol(offs.ctypes.data, odt().itemsize, vals.ctypes.data, vals.size,
-                       None if valid is None else valid.ctypes.data, a.offset if valid is not None else 0, n)
+def _run(op: int, cols: List[ColumnLike], param: int = 0) -> _lib.StrResult:
+    """rogtk_str_transform_host over the columns. Rows of the output: the reference zips its
+    inputs (the shortest wins); the aligned expressions broadcast a 1-row reference next to a
+    longer query column (expressions.rs:344-349)."""
+    chs = [one_chunk(c, rebase=False) for c in cols]
+    lens = [ch.n for ch in chs]
+    scalar_ref = op in (ALIGNED_REF, ALIGNED_QUERY) and lens[0] == 1 and lens[1] > 1
+    n = min(lens[1:]) if scalar_ref else min(lens)
+    chs = [ch if ch.n == n or (scalar_ref and i == 0) else one_chunk(ch.arrow.slice(0, n), rebase=False)
+           for i, ch in enumerate(chs)]
+    descs = (_lib.StrCol * len(chs))(*[ch.desc() for ch in chs])
+    res = _lib.StrResult()
+    _lib.check(_lib.hip().rogtk_str_transform_host(op, descs, len(chs), n, int(param), ctypes.byref(res)))
+    return res
 
 
 def _transform(op: int, cols: List[ColumnLike], param: int = 0):
-    """Rows of the output: the reference zips its inputs (the shortest wins); the aligned
-    expressions broadcast a 1-row reference next to a longer query column
-    (expressions.rs:344-349)."""
-    arrays = [_single(c) for c in cols]
-    lens = [len(a) for a in arrays]
-    scalar_ref = op in (ALIGNED_REF, ALIGNED_QUERY) and lens[0] == 1 and lens[1] > 1
-    n = min(lens[1:]) if scalar_ref else min(lens)
-    arrays = [a if (scalar_ref and i == 0) else a.slice(0, n) for i, a in enumerate(arrays)]
-    keep: list = []
-    descs = (_lib.StrCol * len(arrays))(*[_desc(a, keep) for a in arrays])
-    res = _lib.StrResult()
-    _lib.check(_lib.hip().rogtk_str_transform_host(op, descs, len(arrays), n, int(param), ctypes.byref(res)))
-    return _take_result(res, n)
-
-
-def _take_result(res: _lib.StrResult, n: int):
-    """Copies of a rogtk_str_result's buffers; frees the result."""
-    lib = _lib.hip()
-    try:
-        offs = np.ctypeslib.as_array(ctypes.cast(res.offsets, ctypes.POINTER(ctypes.c_int64)), (n + 1,)).copy()
-        vals = np.ctypeslib.as_array(ctypes.cast(res.values, ctypes.POINTER(ctypes.c_uint8)),
-                                     (max(res.values_len, 1),))[:res.values_len].copy()
-        nbytes = max((n + 63) // 64 * 8, 8)
-        bits = np.ctypeslib.as_array(ctypes.cast(res.validity, ctypes.POINTER(ctypes.c_uint8)), (nbytes,)).copy()
-        nulls = int(res.null_count)
-    finally:
-        lib.rogtk_str_result_free(ctypes.byref(res))
-    return n, offs, vals, bits, nulls
-
-
-def _string_array(n, offs, vals, bits, nulls) -> pa.Array:
-    vb = pa.py_buffer(bits) if nulls else None
-    return pa.Array.from_buffers(pa.large_string(), n, [vb, pa.py_buffer(offs), pa.py_buffer(vals)], null_count=nulls)
+    """The output's raw buffers: (n, offsets, values, validity bytes, null_count)."""
+    return _lib.take_str_buffers(_run(op, cols, param))
 
 
 def reverse_complement(column: ColumnLike) -> pa.Array:
     """reverse_complement_series (expressions.rs:957-977): chars reversed, A<->T, C<->G."""
-    return _string_array(*_transform(REVCOMP, [column]))
+    return _lib.take_str(_run(REVCOMP, [column]))
 
 
 def parse_cigar(column: ColumnLike, block_dels: bool = False) -> pa.Array:
     """parse_cigar_series (expressions.rs:450-505): "D,pos,len|I,pos,len|..."."""
-    return _string_array(*_transform(PARSE_CIGAR, [column], int(bool(block_dels))))
+    return _lib.take_str(_run(PARSE_CIGAR, [column], int(bool(block_dels))))
 
 
 def phred_to_numeric_str(column: ColumnLike, base: int = 33) -> pa.Array:
     """phred_to_numeric_series_str (expressions.rs:632-665): "q1|q2|..."."""
-    return _string_array(*_transform(PHRED_STR, [column], base))
+    return _lib.take_str(_run(PHRED_STR, [column], base))
 
 
 def phred_to_numeric(column: ColumnLike, base: int = 33) -> pa.Array:
@@ -116,7 +79,7 @@ def phred_to_numeric(column: ColumnLike, base: int = 33) -> pa.Array:
 
 def extract_cigar_insertions(seq_col: ColumnLike, cigar_col: ColumnLike) -> pa.Array:
     """extract_cigar_insertions_expr (expressions.rs:207-251): "pos:SEQ|..." sorted by pos."""
-    return _string_array(*_transform(CIGAR_INSERTIONS, [seq_col, cigar_col]))
+    return _lib.take_str(_run(CIGAR_INSERTIONS, [seq_col, cigar_col]))
 
 
 class DnaNamespace:
@@ -138,15 +101,15 @@ class CigarNamespace:
 
     def enrich_insertions(self, seq_col: ColumnLike, cigar_col: ColumnLike):
         """enrich_allele_insertions_expr (expressions.rs:172-205): [pos:NI] -> [pos:NI:SEQ]."""
-        return _string_array(*_transform(ENRICH_ALLELE, [self._c, seq_col, cigar_col]))
+        return _lib.take_str(_run(ENRICH_ALLELE, [self._c, seq_col, cigar_col]))
 
     def align_to_ref(self, query_col: ColumnLike, cigar_col: ColumnLike):
         """cigar_aligned_ref_expr (expressions.rs:338-394)."""
-        return _string_array(*_transform(ALIGNED_REF, [self._c, query_col, cigar_col]))
+        return _lib.take_str(_run(ALIGNED_REF, [self._c, query_col, cigar_col]))
 
     def align_to_query(self, query_col: ColumnLike, cigar_col: ColumnLike):
         """cigar_aligned_query_expr (expressions.rs:396-444)."""
-        return _string_array(*_transform(ALIGNED_QUERY, [self._c, query_col, cigar_col]))
+        return _lib.take_str(_run(ALIGNED_QUERY, [self._c, query_col, cigar_col]))
 
 
 # ------------------------------------------------------------------ fuzzy
@@ -200,24 +163,21 @@ class FuzzyProgram:
         return buf.raw[: need.value].decode("utf-8", "replace")
 
     def contains(self, column: ColumnLike) -> pa.Array:
-        a = _single(column)
-        n = len(a)
-        keep: list = []
-        d = _desc(a, keep)
+        ch = one_chunk(column, rebase=False)
+        n = ch.n
+        d = ch.desc()
         bits = np.zeros(max((n + 63) // 64, 1), dtype=np.uint64)
         vbits = np.zeros_like(bits)
-        _lib.call("rogtk_fuzzy_contains_host", self._h, ctypes.byref(d), bits.ctypes.data, vbits.ctypes.data)
-        nulls = a.null_count
+        _lib.call("rogtk_fuzzy_contains_host", self._h, ctypes.byref(d), _lib.ptr(bits), _lib.ptr(vbits))
+        nulls = ch.arrow.null_count
         return pa.Array.from_buffers(pa.bool_(), n, [pa.py_buffer(vbits) if nulls else None, pa.py_buffer(bits)],
                                      null_count=nulls)
 
     def replace(self, column: ColumnLike, replace_all: bool) -> pa.Array:
-        a = _single(column)
-        keep: list = []
-        d = _desc(a, keep)
+        d = one_chunk(column, rebase=False).desc()
         res = _lib.StrResult()
         _lib.call("rogtk_fuzzy_replace_host", self._h, ctypes.byref(d), int(bool(replace_all)), ctypes.byref(res))
-        return _string_array(*_take_result(res, len(a)))
+        return _lib.take_str(res)
 
     def close(self) -> None:
         if self._h is not None and self._h.value:

@@ -73,10 +73,10 @@ def test_kwargs_pickle_parses(kwargs, text):
 
 
 def _col(items):
-    from rogtk_amd.correct import _desc, _one_chunk
+    from rogtk_amd.columns import one_chunk
 
-    ch = _one_chunk(pa.array(items, type=pa.large_binary()))
-    return ch, _desc(ch)
+    ch = one_chunk(pa.array(items, type=pa.large_binary()))
+    return ch, ch.desc()
 
 
 def test_max_distance_2_is_unsupported():

@@ -72,12 +72,13 @@ def _same_column(got: pa.Array, want):
 def _transform(S, op, arrays, n, param=0):
     """rogtk_str_transform_host on pyarrow arrays as they are (slices included), n output rows."""
     from rogtk_amd import _lib
+    from rogtk_amd.columns import one_chunk
 
-    keep: list = []
-    descs = (_lib.StrCol * len(arrays))(*[S._desc(a, keep) for a in arrays])
+    keep = [one_chunk(a, rebase=False) for a in arrays]
+    descs = (_lib.StrCol * len(arrays))(*[ch.desc() for ch in keep])
     res = _lib.StrResult()
     _lib.check(_lib.hip().rogtk_str_transform_host(C.OPS[op], descs, len(arrays), n, param, ctypes.byref(res)))
-    return S._string_array(*S._take_result(res, n))
+    return _lib.take_str(res)
 
 
 def _dna(rng, n, lo, hi):
@@ -246,7 +247,7 @@ def test_pinned_input_goes_by_direct_dma(S):
         desc = (_lib.StrCol * 1)(_lib.StrCol(blocks[0], 8, blocks[1], n * w + 1, None, 0, n))
         res = _lib.StrResult()
         _lib.check(lib.rogtk_str_transform_host(C.OPS["revcomp"], desc, 1, n, 0, ctypes.byref(res)))
-        _, goff, gval, _, nulls = S._take_result(res, n)
+        _, goff, gval, _, nulls = _lib.take_str_buffers(res)
     finally:
         for b in blocks:
             lib.rogtk_host_free(b)
@@ -258,12 +259,13 @@ def test_pinned_input_goes_by_direct_dma(S):
 @pytest.mark.parametrize("case", C.OVER_CAP, ids=lambda c: c["name"])
 def test_over_cap_leaves_the_result_zeroed(S, case):
     from rogtk_amd import _lib
+    from rogtk_amd.columns import one_chunk
 
     lib = _lib.hip()
     arrays = [pa.array(c, type=pa.large_string()) for c in case["cols"]]
     n = max(len(a) for a in arrays)
-    keep: list = []
-    descs = (_lib.StrCol * len(arrays))(*[S._desc(a, keep) for a in arrays])
+    keep = [one_chunk(a, rebase=False) for a in arrays]
+    descs = (_lib.StrCol * len(arrays))(*[ch.desc() for ch in keep])
     res = _lib.StrResult()
     res.n = 77
     rc = lib.rogtk_str_transform_host(C.OPS[case["op"]], descs, len(arrays), n, case["param"], ctypes.byref(res))
