@@ -14,6 +14,7 @@ Drop-in surface (mirrors rogtk/__init__.py's `umi` / `hamming` namespaces):
     rg.umi_correct(umis, method="directional", groups=cell_ids)  # within each key (§4d)
     rg.BarcodeWhitelist(whitelist).correct(cbcs) # whitelist index per row: groups=res.keys (§4e)
     rg.umi_dedup(umis, 12, score=mapq).keep      # the read to keep per cluster (§4f)
+    rg.umi_count(umis, 12, cells, genes, n_cells, n_genes).to_scipy()  # molecules per (cell, gene) (§4h)
     rg.kmer_spectrum(reads, k=17, min_coverage=20, group_offsets=...)  # H4 (fracture.rs)
     rg.assemble_sequences(group_reads, k=13, min_coverage=1, method="compression")  # H5
     rg.assemble_column_groups(offsets, values, cluster_ids, k=10, min_coverage=5)  # H5, all groups
@@ -49,6 +50,7 @@ from .strings import (  # noqa: F401
 from .correct import UmiCorrection, umi_cluster_summary, umi_correct  # noqa: F401
 from .barcode import BarcodeCorrection, BarcodeNamespace, BarcodeWhitelist, barcode_correct  # noqa: F401
 from .dedup import DedupResult, cluster_best_rows, umi_dedup  # noqa: F401
+from .count import CountMatrix, count_matrix, umi_count  # noqa: F401
 from .api import (  # noqa: F401
     FIELDS,
     KMER_STATS,
@@ -76,4 +78,5 @@ __all__ = [
     "umi_correct", "umi_cluster_summary", "UmiCorrection",
     "BarcodeWhitelist", "BarcodeCorrection", "BarcodeNamespace", "barcode_correct",
     "umi_dedup", "cluster_best_rows", "DedupResult",
+    "umi_count", "count_matrix", "CountMatrix",
 ]

@@ -17,6 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_HERE, "librogtk_hip.so")
 SYNTH_LIB_PATH = os.path.join(_HERE, "_synth", "librogtk_synth.so")
 DEDUP_LIB_PATH = os.path.join(_HERE, "_dedup", "librogtk_dedup.so")
+COUNT_LIB_PATH = os.path.join(_HERE, "_count", "librogtk_count.so")
 
 ROGTK_OK = 0
 ROGTK_E_INVALID = 1
@@ -264,6 +265,12 @@ SIGNATURES = {
     "rogtk_cluster_best_rows_host": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _P_I64],
     "rogtk_cluster_best_geometry": [_P_I64],
     "rogtk_cluster_best_set_knobs": [_i32, _i32],
+    # the UMI count matrix: exported by librogtk_count.so (count())
+    "rogtk_count_matrix_temp_bytes": [_i64, _i64, _i64, _i64, _i64, _P_I64],
+    "rogtk_count_matrix": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp],
+    "rogtk_count_matrix_host": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
+    "rogtk_count_matrix_geometry": [_P_I64],
+    "rogtk_count_matrix_set_phases": [_i32],
     "rogtk_profile_enable": [_i32],
     "rogtk_profile_select": [ctypes.c_char_p],
     "rogtk_profile_reset": [],
@@ -354,6 +361,30 @@ def dedup() -> ctypes.CDLL:
     return _dedup
 
 
+COUNT_PREFIX = "rogtk_count_matrix"
+_count = None
+
+
+def count() -> ctypes.CDLL:
+    """Load librogtk_count.so (the rogtk_count_matrix* entries), after librogtk_hip.so, whose
+    error string it shares. Loaded at the feature's first use, not with the package."""
+    global _count
+    hip()
+    with _lock:
+        if _count is None:
+            if not os.path.exists(COUNT_LIB_PATH):
+                raise RogtkError(ROGTK_E_NODEVICE, f"{COUNT_LIB_PATH} is missing: run make -C rogtk_amd/csrc. "
+                                                   "There is no CPU fallback.")
+            lib = ctypes.CDLL(COUNT_LIB_PATH)
+            for name, argtypes in SIGNATURES.items():
+                if name.startswith(COUNT_PREFIX):
+                    fn = getattr(lib, name)  # a missing export fails here
+                    fn.argtypes = argtypes
+                    fn.restype = ctypes.c_int
+            _count = lib
+    return _count
+
+
 def synth() -> ctypes.CDLL:
     global _synth
     with _lock:
@@ -382,7 +413,7 @@ def check(status: int) -> None:
 
 
 def call(name: str, *args) -> None:
-    lib = dedup() if name.startswith(DEDUP_PREFIX) else hip()
+    lib = dedup() if name.startswith(DEDUP_PREFIX) else count() if name.startswith(COUNT_PREFIX) else hip()
     check(getattr(lib, name)(*args))
 
 
