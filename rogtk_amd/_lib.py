@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import sys
 import threading
 
 import numpy as np
@@ -338,51 +339,44 @@ def hip() -> ctypes.CDLL:
 
 
 DEDUP_PREFIX = "rogtk_cluster_best_"
-_dedup = None
+COUNT_PREFIX = "rogtk_count_matrix"
+# the libraries beside librogtk_hip.so, each with the entries of one prefix: name -> (prefix, path)
+SIDE_LIBS = {"dedup": (DEDUP_PREFIX, DEDUP_LIB_PATH), "count": (COUNT_PREFIX, COUNT_LIB_PATH)}
+_side = {}
+_route = {}  # entry name -> the loader that serves it ("hip" or a key of SIDE_LIBS), filled by call()
+_this = sys.modules[__name__]
+
+
+def _side_lib(which: str) -> ctypes.CDLL:
+    """Load a side library, after librogtk_hip.so, whose error string it shares. Loaded at the
+    feature's first use, not with the package."""
+    if which in _side:
+        return _side[which]
+    prefix, path = SIDE_LIBS[which]
+    hip()
+    with _lock:
+        if which not in _side:
+            if not os.path.exists(path):
+                raise RogtkError(ROGTK_E_NODEVICE, f"{path} is missing: run make -C rogtk_amd/csrc. "
+                                                   "There is no CPU fallback.")
+            lib = ctypes.CDLL(path)
+            for name, argtypes in SIGNATURES.items():
+                if name.startswith(prefix):
+                    fn = getattr(lib, name)  # a missing export fails here
+                    fn.argtypes = argtypes
+                    fn.restype = ctypes.c_int
+            _side[which] = lib
+    return _side[which]
 
 
 def dedup() -> ctypes.CDLL:
-    """Load librogtk_dedup.so (the rogtk_cluster_best_* entries), after librogtk_hip.so, whose
-    error string it shares. Loaded at the feature's first use, not with the package."""
-    global _dedup
-    hip()
-    with _lock:
-        if _dedup is None:
-            if not os.path.exists(DEDUP_LIB_PATH):
-                raise RogtkError(ROGTK_E_NODEVICE, f"{DEDUP_LIB_PATH} is missing: run make -C rogtk_amd/csrc. "
-                                                   "There is no CPU fallback.")
-            lib = ctypes.CDLL(DEDUP_LIB_PATH)
-            for name, argtypes in SIGNATURES.items():
-                if name.startswith(DEDUP_PREFIX):
-                    fn = getattr(lib, name)  # a missing export fails here
-                    fn.argtypes = argtypes
-                    fn.restype = ctypes.c_int
-            _dedup = lib
-    return _dedup
-
-
-COUNT_PREFIX = "rogtk_count_matrix"
-_count = None
+    """librogtk_dedup.so (the rogtk_cluster_best_* entries)."""
+    return _side_lib("dedup")
 
 
 def count() -> ctypes.CDLL:
-    """Load librogtk_count.so (the rogtk_count_matrix* entries), after librogtk_hip.so, whose
-    error string it shares. Loaded at the feature's first use, not with the package."""
-    global _count
-    hip()
-    with _lock:
-        if _count is None:
-            if not os.path.exists(COUNT_LIB_PATH):
-                raise RogtkError(ROGTK_E_NODEVICE, f"{COUNT_LIB_PATH} is missing: run make -C rogtk_amd/csrc. "
-                                                   "There is no CPU fallback.")
-            lib = ctypes.CDLL(COUNT_LIB_PATH)
-            for name, argtypes in SIGNATURES.items():
-                if name.startswith(COUNT_PREFIX):
-                    fn = getattr(lib, name)  # a missing export fails here
-                    fn.argtypes = argtypes
-                    fn.restype = ctypes.c_int
-            _count = lib
-    return _count
+    """librogtk_count.so (the rogtk_count_matrix* entries)."""
+    return _side_lib("count")
 
 
 def synth() -> ctypes.CDLL:
@@ -413,8 +407,10 @@ def check(status: int) -> None:
 
 
 def call(name: str, *args) -> None:
-    lib = dedup() if name.startswith(DEDUP_PREFIX) else count() if name.startswith(COUNT_PREFIX) else hip()
-    check(getattr(lib, name)(*args))
+    which = _route.get(name)
+    if which is None:
+        which = _route[name] = next((w for w, (prefix, _) in SIDE_LIBS.items() if name.startswith(prefix)), "hip")
+    check(getattr(getattr(_this, which)(), name)(*args))  # hip / dedup / count as the module holds them now
 
 
 def version() -> str:

@@ -10,6 +10,7 @@ for that and as Arrow holds them for the entries whose upload rebases (DESIGN.md
 """
 from __future__ import annotations
 
+import ctypes
 from dataclasses import dataclass
 from typing import Iterator, Optional, Sequence, Union
 
@@ -18,6 +19,7 @@ import pyarrow as pa
 
 from . import _lib
 
+NO_ID = 0xFFFFFFFF  # the u32 id of a row that belongs nowhere (what an Arrow null becomes)
 ColumnLike = Union[pa.Array, pa.ChunkedArray, Sequence[Optional[Union[str, bytes]]], np.ndarray]
 
 
@@ -148,6 +150,57 @@ def as_u32(x, name: str, *, rows: Optional[int] = None, nulls_to: Optional[int] 
     if a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
         raise ValueError(f"{name} must hold values in 0..2^32-1")
     return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def largest_plus_one(x) -> int:
+    """1 + the largest value other than 0xFFFFFFFF of a u32 column (numpy array or tensor); 0 if none."""
+    if is_tensor(x):
+        import torch
+
+        x = x.view(torch.int32).to(torch.int64) & NO_ID
+    real = x[x != NO_ID]
+    return int(real.max()) + 1 if len(real) else 0
+
+
+def is_tensor(x) -> bool:
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def u32_tensor(t, name: str, like=None, like_name: str = "") -> None:
+    """A u32 column on a device: a 1-D contiguous int32 / uint32 torch tensor holding the u32 bits,
+    and, beside the call's first tensor `like`, on its device with its length. Else a ValueError."""
+    import torch
+
+    if not is_tensor(t):
+        raise ValueError(f"{name} must be a torch tensor, as {like_name} is")
+    if t.dim() != 1:
+        raise ValueError(f"{name} must be 1-D, got shape {tuple(t.shape)}")
+    if t.dtype not in (torch.int32, torch.uint32) or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous int32 / uint32 device tensor (the u32 bits)")
+    if like is not None and t.device != like.device:
+        raise ValueError(f"{name} is on {t.device}, {like_name} on {like.device}")
+    if like is not None and t.numel() != like.numel():
+        raise ValueError(f"{name} has {t.numel()} rows, {like_name} has {like.numel()}")
+
+
+def dev_ptr(t):
+    """A device tensor (or None) as a pointer argument; NULL for an empty one."""
+    return None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())
+
+
+def device_temp(entry: str, *sizes, device):
+    """The temp buffer of a Level-1 call, sized by its *_temp_bytes entry: a uint8 tensor."""
+    import torch
+
+    tb = ctypes.c_int64(0)
+    _lib.call(entry, *sizes, ctypes.byref(tb))
+    return torch.empty(tb.value, dtype=torch.uint8, device=device)
+
+
+def current_stream() -> ctypes.c_void_p:
+    import torch
+
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def validity_buffer(chunk: HostChunk) -> Optional[pa.Buffer]:

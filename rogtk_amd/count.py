@@ -26,9 +26,8 @@ import numpy as np
 import pyarrow as pa
 
 from . import _lib
-from .columns import as_u32
+from .columns import NO_ID, as_u32, current_stream, dev_ptr, device_temp, is_tensor, largest_plus_one, u32_tensor
 
-NO_ID = 0xFFFFFFFF
 SIZES = ("n_cells", "n_features", "n_molecules")
 
 
@@ -84,10 +83,6 @@ def geometry() -> dict:
     return {"tile": int(out[0]), "scan_block": int(out[1])}
 
 
-def _is_tensor(x) -> bool:
-    return type(x).__module__.split(".")[0] == "torch"
-
-
 def _check_sizes(sizes) -> None:
     for name, v in zip(SIZES, sizes):
         if not 0 <= v <= NO_ID:
@@ -114,53 +109,25 @@ def _count_host(cols, sizes, want_indptr: bool) -> CountMatrix:
                        int(totals[1]), int(totals[2]))
 
 
-def _u32_tensors(cols):
-    """The three columns as torch tensors of one length on one device: the ValueErrors."""
-    import torch
-
-    first = cols[0]
-    for name, t in zip(("cell", "feature", "molecule"), cols):
-        if not _is_tensor(t):
-            raise ValueError(f"{name} must be a torch tensor, as cell is")
-        if t.dim() != 1:
-            raise ValueError(f"{name} must be 1-D, got shape {tuple(t.shape)}")
-        if t.dtype not in (torch.int32, torch.uint32) or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous int32 / uint32 device tensor (the u32 bits)")
-        if t.device != first.device:
-            raise ValueError(f"{name} is on {t.device}, cell on {first.device}")
-        if t.numel() != first.numel():
-            raise ValueError(f"{name} has {t.numel()} rows, cell has {first.numel()}")
-    return first.device, first.numel()
-
-
-def _largest_plus_one_tensor(t) -> int:
-    import torch
-
-    v = t.view(torch.int32).to(torch.int64) & NO_ID
-    v = v[v != NO_ID]
-    return int(v.max().item()) + 1 if v.numel() else 0
-
-
 def _count_device(cols, sizes, want_indptr: bool) -> CountMatrix:
     """torch tensors in and out, on the columns' device and the current stream (synchronised once,
     for totals). The u32 columns are int32 (or uint32) tensors holding the u32 bits."""
     import torch
 
-    dev, n = _u32_tensors(cols)
-    sizes = [s if s >= 0 else _largest_plus_one_tensor(t) for s, t in zip(sizes, cols)]
+    for name, t in zip(("cell", "feature", "molecule"), cols):
+        u32_tensor(t, name, cols[0], "cell")
+    dev, n = cols[0].device, cols[0].numel()
+    sizes = [s if s >= 0 else largest_plus_one(t) for s, t in zip(sizes, cols)]
     _check_sizes(sizes)
     nc = sizes[0]
     cap = _capacity(n, sizes)
     with torch.cuda.device(dev):
-        tb = ctypes.c_int64(0)
-        _lib.call("rogtk_count_matrix_temp_bytes", n, *sizes, cap, ctypes.byref(tb))
-        temp = torch.empty(tb.value, dtype=torch.uint8, device=dev)
+        temp = device_temp("rogtk_count_matrix_temp_bytes", n, *sizes, cap, device=dev)
         out = [torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(4)]
         indptr = torch.empty(nc + 1, dtype=torch.int64, device=dev) if want_indptr else None
         totals = torch.empty(3, dtype=torch.int64, device=dev)
-        p = lambda t: None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())
-        _lib.call("rogtk_count_matrix", p(cols[0]), p(cols[1]), p(cols[2]), n, *sizes, *(p(t) for t in out), cap,
-                  p(indptr), p(totals), p(temp), tb.value, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.call("rogtk_count_matrix", *map(dev_ptr, cols), n, *sizes, *map(dev_ptr, out), cap,
+                  *map(dev_ptr, (indptr, totals, temp)), temp.numel(), current_stream())
         tot = totals.cpu().tolist()
     nnz = min(int(tot[0]), cap)
     return CountMatrix(*(t[:nnz] for t in out), indptr, (nc, sizes[1]), nnz, int(tot[1]), int(tot[2]))
@@ -174,15 +141,12 @@ def count_matrix(cell, feature, molecule, n_cells: int = -1, n_features: int = -
     none). Host arrays (numpy / Arrow) give Arrow out; torch device tensors give torch tensors
     out on the same device. indptr=False leaves the CSR row pointer out."""
     sizes = [int(n_cells), int(n_features), int(n_molecules)]
-    if _is_tensor(cell):
+    if is_tensor(cell):
         return _count_device((cell, feature, molecule), sizes, bool(indptr))
     cols = [as_u32(cell, "cell", nulls_to=NO_ID)]
     cols.append(as_u32(feature, "feature", rows=cols[0].size, nulls_to=NO_ID))
     cols.append(as_u32(molecule, "molecule", rows=cols[0].size, nulls_to=NO_ID))
-    for i, c in enumerate(cols):
-        if sizes[i] < 0:
-            real = c[c != NO_ID]
-            sizes[i] = int(real.max()) + 1 if real.size else 0
+    sizes = [s if s >= 0 else largest_plus_one(c) for s, c in zip(sizes, cols)]
     _check_sizes(sizes)
     return _count_host(cols, sizes, bool(indptr))
 

@@ -1745,6 +1745,7 @@ int cluster_layout(int L, int64_t max_distinct, ClusterLayout* o) {
     // space); by rank at L = 12 measured slower (two dependent gathers per exception row)
     c.label_by_code = L <= 13;
     int64_t off = 0;
+    // not column_util.h's Carve: a piece of 0 bytes takes 0 here, 256 there (al), and the sizes are public
     auto take = [&](int64_t bytes) {
         const int64_t at = off;
         off += (bytes + 255) / 256 * 256;

@@ -11,6 +11,16 @@ namespace rogtk {
 
 inline size_t al(size_t b) { return (std::max<size_t>(b, 1) + 255) / 256 * 256; }
 
+// a byte range carved into pieces of al() bytes: take() gives a piece's offset, total the sum so far
+struct Carve {
+    size_t total = 0;
+    size_t take(size_t bytes) {
+        const size_t at = total;
+        total += al(bytes);
+        return at;
+    }
+};
+
 // workgroups of `block` threads over n items, at most cap (grid-stride kernels pass one)
 inline unsigned grid_for(int64_t n, int block, int64_t cap = 0x7FFFFFFF) {
     return (unsigned)std::min<int64_t>(cap, std::max<int64_t>(1, (n + block - 1) / block));

@@ -265,24 +265,19 @@ int packed_layout(int64_t n, int L, int64_t n_clusters, PackedLayout* p) {
     ROGTK_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, sb, (const uint32_t*)nullptr, (uint32_t*)nullptr,
                                                        (const uint32_t*)nullptr, (uint32_t*)nullptr,
                                                        (int)std::max<int64_t>(n, 1), 0, 2 * L));
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += al(bytes);
-        return at;
-    };
-    p->off_cnt = take(16);
-    p->off_votes = take((size_t)n_clusters * 8);
-    for (int k = 0; k < 2; ++k) p->off_key[k] = take((size_t)n * 4);
-    for (int k = 0; k < 2; ++k) p->off_val[k] = take((size_t)n * 4);
+    Carve c;
+    p->off_cnt = c.take(16);
+    p->off_votes = c.take((size_t)n_clusters * 8);
+    for (int k = 0; k < 2; ++k) p->off_key[k] = c.take((size_t)n * 4);
+    for (int k = 0; k < 2; ++k) p->off_val[k] = c.take((size_t)n * 4);
     p->sort_bytes = sb;
-    p->off_sort = take(sb);
+    p->off_sort = c.take(sb);
     p->off_tab = p->off_idtab = 0;
     if (L <= kTableMaxLen) {
-        p->off_tab = take((size_t)4 << (2 * L));
-        p->off_idtab = take((size_t)4 << (2 * L));
+        p->off_tab = c.take((size_t)4 << (2 * L));
+        p->off_idtab = c.take((size_t)4 << (2 * L));
     }
-    p->total = o;
+    p->total = c.total;
     return ROGTK_OK;
 }
 

@@ -13,8 +13,7 @@
 //   sort    hipcub radix sort of the keys over bits [0, cb + fb + mb)
 //   flags   per sorted position: live, new molecule (key differs from its predecessor), new entry
 //           (key >> mb differs); per tile the popcounts of the three ballots
-//   scan    exclusive scan of the tile popcounts by one workgroup (no look-back, nothing spins);
-//           the three totals
+//   scan    exclusive scan of the tile popcounts and the three totals (k_tile_scan of id_columns.h)
 //   emit    every new-entry position i gets e = offset[tile] + rank in tile and writes the
 //           entry's cell and feature, row_start[e] = i and mol_start[e] = new molecules before i
 //   diff    n_reads[e] = row_start[e + 1] - row_start[e], n_umis[e] = mol_start[e + 1] -
@@ -29,7 +28,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "../../include/rogtk_count.h"
-#include "column_util.h"
+#include "id_columns.h"
 
 namespace rogtk {
 namespace {
@@ -39,7 +38,6 @@ constexpr int kWaves = kBlock / 64;
 constexpr int kSteps = 8;                     // 64-row steps per wave and tile
 constexpr int kTile = kBlock * kSteps;        // 2048 sorted positions per flag / emit tile
 constexpr int kWaveRows = 64 * kSteps;        // consecutive positions of one wave
-constexpr int kScanBlock = 1024;
 constexpr int64_t kMaxSize = (1ll << 32) - 1;  // sizes are 0..2^32-1
 constexpr size_t kTempAlign = 256;            // the call rounds temp up to this
 
@@ -87,20 +85,6 @@ __device__ __forceinline__ unsigned long long pack_key(uint32_t c, uint32_t f, u
     if (c < p.nc && f < p.nf && m < p.nm)
         return ((unsigned long long)c << p.fm) | ((unsigned long long)f << p.mb) | (unsigned long long)m;
     return (unsigned long long)p.nc << p.fm;
-}
-
-// rows r0 .. r0 + 3 of p (one 16-byte load when the column allows it), `fill` past n
-__device__ __forceinline__ void load4(const uint32_t* __restrict__ p, int64_t r0, int64_t n, bool vec, uint32_t fill,
-                                      uint32_t (&v)[4]) {
-    if (vec && r0 + 4 <= n) {
-        const u32x4_t q = stream_load((const u32x4_t*)(p + r0));
-        v[0] = q.x;
-        v[1] = q.y;
-        v[2] = q.z;
-        v[3] = q.w;
-    } else {
-        for (int k = 0; k < 4; ++k) v[k] = r0 + k < n ? p[r0 + k] : fill;
-    }
 }
 
 // key[] is 16-byte aligned (the call aligns temp), so rows r0 .. r0 + 3 take two 16-byte stores
@@ -172,48 +156,6 @@ k_count_flags(const unsigned long long* __restrict__ key, int64_t n, CountKey p,
         uint32_t t = 0;
         for (int w = 0; w < kWaves; ++w) t += wsum[threadIdx.x][w];
         counts[(int64_t)threadIdx.x * nt + blockIdx.x] = t;
-    }
-}
-
-// exclusive scan of the entry and molecule popcounts, the sum of the live ones; one workgroup.
-// totals = {entries, live rows, molecules}
-__global__ void __launch_bounds__(kScanBlock)
-k_count_scan(const uint32_t* __restrict__ counts, int64_t nt, uint32_t* __restrict__ offs,
-             int64_t* __restrict__ totals) {
-    __shared__ uint32_t wtot[3][kScanBlock / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t carry[3] = {0u, 0u, 0u};
-    for (int64_t base = 0; base < nt; base += kScanBlock) {
-        const int64_t i = base + threadIdx.x;
-        uint32_t v[3], s[3];
-        for (int a = 0; a < 3; ++a) {
-            v[a] = i < nt ? counts[(int64_t)a * nt + i] : 0u;
-            s[a] = v[a];
-        }
-        for (int d = 1; d < 64; d <<= 1)
-            for (int a = 0; a < 3; ++a) {
-                const uint32_t u = __shfl_up(s[a], d);
-                if (lane >= d) s[a] += u;
-            }
-        if (lane == 63)
-            for (int a = 0; a < 3; ++a) wtot[a][wave] = s[a];
-        __syncthreads();
-        for (int a = 0; a < 3; ++a) {
-            uint32_t before = 0, total = 0;
-            for (int k = 0; k < kScanBlock / 64; ++k) {
-                const uint32_t t = wtot[a][k];
-                if (k < wave) before += t;
-                total += t;
-            }
-            if (a < 2 && i < nt) offs[(int64_t)a * nt + i] = carry[a] + before + s[a] - v[a];
-            carry[a] += total;
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        totals[0] = (int64_t)carry[0];
-        totals[1] = (int64_t)carry[2];
-        totals[2] = (int64_t)carry[1];
     }
 }
 
@@ -302,6 +244,9 @@ k_count_indptr(const int64_t* __restrict__ totals, int64_t capacity, const uint3
     indptr[c] = lo;
 }
 
+// planes {new entry, new molecule, live}: offsets for the first two, totals = {entries, live, molecules}
+constexpr auto k_count_scan = k_tile_scan<2, 0, 2, 1>;
+
 struct CountLayout {
     size_t off_key, off_sorted, off_cub, off_counts, off_offs, off_row, off_mol, total;
     size_t cub_bytes;
@@ -323,20 +268,15 @@ int count_layout(int64_t n, int64_t capacity, CountLayout* out) {
         p.cub_bytes = (size_t)n * 12 + (1u << 20);
     }
     const int64_t slots = std::min(capacity, n) + 1;  // entries <= n
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += al(bytes);
-        return at;
-    };
-    p.off_key = take((size_t)n * 8);
-    p.off_sorted = take((size_t)n * 8);
-    p.off_cub = take(p.cub_bytes);
-    p.off_counts = take((size_t)p.tiles * 3 * 4);
-    p.off_offs = take((size_t)p.tiles * 2 * 4);
-    p.off_row = take((size_t)slots * 4);
-    p.off_mol = take((size_t)slots * 4);
-    p.total = o + kTempAlign;  // room to round the caller's pointer up
+    Carve c;
+    p.off_key = c.take((size_t)n * 8);
+    p.off_sorted = c.take((size_t)n * 8);
+    p.off_cub = c.take(p.cub_bytes);
+    p.off_counts = c.take((size_t)p.tiles * 3 * 4);
+    p.off_offs = c.take((size_t)p.tiles * 2 * 4);
+    p.off_row = c.take((size_t)slots * 4);
+    p.off_mol = c.take((size_t)slots * 4);
+    p.total = c.total + kTempAlign;  // room to round the caller's pointer up
     *out = p;
     return ROGTK_OK;
 }
@@ -355,7 +295,7 @@ bool no_entries(const CountArgs& a) { return a.n == 0 || a.n_cells == 0 || a.n_f
 // The argument rules of both levels (include/rogtk_count.h), before any device work. The width
 // of the key is decided here, from the three sizes alone.
 int check_sizes(const char* name, int64_t n, int64_t nc, int64_t nf, int64_t nm) {
-    ROGTK_REQUIRE(n >= 0 && n < (1ll << 31), ROGTK_E_INVALID, "%s: n %lld outside 0..2^31-1", name, (long long)n);
+    if (int rc = check_rows(name, n)) return rc;
     ROGTK_REQUIRE(nc >= 0 && nc <= kMaxSize, ROGTK_E_INVALID, "%s: n_cells %lld outside 0..2^32-1", name,
                   (long long)nc);
     ROGTK_REQUIRE(nf >= 0 && nf <= kMaxSize, ROGTK_E_INVALID, "%s: n_features %lld outside 0..2^32-1", name,
@@ -431,21 +371,11 @@ int launch_count_matrix(const CountArgs& a, const CountLayout& p, void* temp, hi
     return ROGTK_OK;
 }
 
-// one device allocation of a host call, released on every way out
-struct HostCallMem {
-    uint8_t* p = nullptr;
-    ~HostCallMem() {
-        if (p) (void)hipFree(p);
-    }
-};
-
 }  // namespace
 }  // namespace rogtk
 
 // ------------------------------------------------------------------ C ABI
-// The entries live in a library of their own (rogtk_amd/_count/librogtk_count.so), which links
-// librogtk_hip.so for the shared error string (rogtk_last_error); librogtk_hip.so itself is
-// built exactly as without this file.
+// The entries live in a library of their own, rogtk_amd/_count/librogtk_count.so.
 using namespace rogtk;
 
 extern "C" {
@@ -508,56 +438,38 @@ int rogtk_count_matrix_host(const uint32_t* cell, const uint32_t* feature, const
     if (int rc = check_count("count_matrix_host", h)) return rc;
     CountLayout p;
     if (int rc = count_layout(n, capacity, &p)) return rc;
-    int devices = 0;
-    if (hipGetDeviceCount(&devices) != hipSuccess || devices <= 0) {
-        set_error("no HIP device available (librogtk_count needs an MI355X / gfx950 GPU)");
-        return ROGTK_E_NODEVICE;
-    }
     // one allocation, the whole call on the default stream: the columns, the outputs, temp
     const int64_t cap = std::min(capacity, n);  // entries <= n: what the device can write
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += al(bytes);
-        return at;
-    };
-    const size_t o_cell = take((size_t)n * 4), o_feat = take((size_t)n * 4), o_mol = take((size_t)n * 4),
-                 o_ec = take((size_t)cap * 4), o_ef = take((size_t)cap * 4), o_nu = take((size_t)cap * 4),
-                 o_nr = take((size_t)cap * 4), o_ip = take(indptr ? (size_t)(n_cells + 1) * 8 : 0), o_tot = take(24),
-                 o_temp = take(p.total);
-    HostCallMem m;
-    ROGTK_HIP_CHECK(hipMalloc((void**)&m.p, o));
-    uint8_t* d = m.p;
-    if (n > 0) {
-        ROGTK_HIP_CHECK(hipMemcpy(d + o_cell, cell, (size_t)n * 4, hipMemcpyHostToDevice));
-        ROGTK_HIP_CHECK(hipMemcpy(d + o_feat, feature, (size_t)n * 4, hipMemcpyHostToDevice));
-        ROGTK_HIP_CHECK(hipMemcpy(d + o_mol, molecule, (size_t)n * 4, hipMemcpyHostToDevice));
-    }
+    HostCall m;
+    const size_t o_cell = m.take((size_t)n * 4), o_feat = m.take((size_t)n * 4), o_mol = m.take((size_t)n * 4),
+                 o_ec = m.take((size_t)cap * 4), o_ef = m.take((size_t)cap * 4), o_nu = m.take((size_t)cap * 4),
+                 o_nr = m.take((size_t)cap * 4), o_ip = m.take(indptr ? (size_t)(n_cells + 1) * 8 : 0),
+                 o_tot = m.take(24), o_temp = m.take(p.total);
+    if (int rc = m.open("librogtk_count")) return rc;
+    if (int rc = m.in(o_cell, cell, (size_t)n * 4)) return rc;
+    if (int rc = m.in(o_feat, feature, (size_t)n * 4)) return rc;
+    if (int rc = m.in(o_mol, molecule, (size_t)n * 4)) return rc;
     CountArgs a = h;
-    a.cell = (const uint32_t*)(d + o_cell);
-    a.feature = (const uint32_t*)(d + o_feat);
-    a.molecule = (const uint32_t*)(d + o_mol);
-    a.entry_cell = (uint32_t*)(d + o_ec);
-    a.entry_feature = (uint32_t*)(d + o_ef);
-    a.n_umis = (uint32_t*)(d + o_nu);
-    a.n_reads = n_reads ? (uint32_t*)(d + o_nr) : nullptr;
+    a.cell = m.at<uint32_t>(o_cell);
+    a.feature = m.at<uint32_t>(o_feat);
+    a.molecule = m.at<uint32_t>(o_mol);
+    a.entry_cell = m.at<uint32_t>(o_ec);
+    a.entry_feature = m.at<uint32_t>(o_ef);
+    a.n_umis = m.at<uint32_t>(o_nu);
+    a.n_reads = n_reads ? m.at<uint32_t>(o_nr) : nullptr;
     a.capacity = cap;  // an entry index never reaches n, so the device sees the same cut
-    a.indptr = indptr ? (int64_t*)(d + o_ip) : nullptr;
-    a.totals = (int64_t*)(d + o_tot);
-    if (int rc = launch_count_matrix(a, p, d + o_temp, nullptr)) return rc;
-    // blocking copies on the default stream: ordered behind the kernels
-    ROGTK_HIP_CHECK(hipMemcpy(totals, d + o_tot, 24, hipMemcpyDeviceToHost));
+    a.indptr = indptr ? m.at<int64_t>(o_ip) : nullptr;
+    a.totals = m.at<int64_t>(o_tot);
+    if (int rc = launch_count_matrix(a, p, m.at<void>(o_temp), nullptr)) return rc;
+    if (int rc = m.out(totals, o_tot, 24)) return rc;
     ROGTK_REQUIRE(totals[0] >= 0 && totals[0] <= n, ROGTK_E_HIP, "count_matrix_host: %lld entries outside 0..%lld",
                   (long long)totals[0], (long long)n);
-    const int64_t wrote = std::min(totals[0], cap);
-    if (wrote > 0) {
-        ROGTK_HIP_CHECK(hipMemcpy(entry_cell, d + o_ec, (size_t)wrote * 4, hipMemcpyDeviceToHost));
-        ROGTK_HIP_CHECK(hipMemcpy(entry_feature, d + o_ef, (size_t)wrote * 4, hipMemcpyDeviceToHost));
-        ROGTK_HIP_CHECK(hipMemcpy(n_umis, d + o_nu, (size_t)wrote * 4, hipMemcpyDeviceToHost));
-        if (n_reads) ROGTK_HIP_CHECK(hipMemcpy(n_reads, d + o_nr, (size_t)wrote * 4, hipMemcpyDeviceToHost));
-    }
-    if (indptr) ROGTK_HIP_CHECK(hipMemcpy(indptr, d + o_ip, (size_t)(n_cells + 1) * 8, hipMemcpyDeviceToHost));
-    return ROGTK_OK;
+    const size_t wrote = (size_t)std::min(totals[0], cap) * 4;
+    if (int rc = m.out(entry_cell, o_ec, wrote)) return rc;
+    if (int rc = m.out(entry_feature, o_ef, wrote)) return rc;
+    if (int rc = m.out(n_umis, o_nu, wrote)) return rc;
+    if (int rc = m.out(n_reads, o_nr, wrote)) return rc;
+    return m.out(indptr, o_ip, (size_t)(n_cells + 1) * 8);
 }
 
 }  // extern "C"

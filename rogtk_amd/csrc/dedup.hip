@@ -20,8 +20,8 @@
 //   keep     each lane re-forms its key and compares it with votes[id]; the ballot of a wave
 //            is the 64-row keep word (rows past n and skipped rows give 0, so the padding bits
 //            are written as zero); a workgroup also leaves the popcount of its kKeepTile rows.
-//   compact  exclusive scan of the tile popcounts by one workgroup (no look-back, nothing
-//            spins), then a scatter of the set bits of every tile, ascending by construction.
+//   compact  exclusive scan of the tile popcounts (k_tile_scan of id_columns.h), then a scatter
+//            of the set bits of every tile, ascending by construction.
 //   decode   votes[c] -> best_row[c] (-1 without rows), best_score[c].
 //
 // max and add commute, so the answer does not depend on geometry or scheduling. Enqueue-only:
@@ -29,7 +29,7 @@
 #include <atomic>
 
 #include "../../include/rogtk_dedup.h"
-#include "column_util.h"
+#include "id_columns.h"
 
 namespace rogtk {
 namespace {
@@ -41,7 +41,6 @@ constexpr int kSlotBits = 11;
 constexpr int kSlots = 1 << kSlotBits;  // 32 KiB of LDS
 constexpr int kProbes = 4;
 constexpr int kKeepTile = 64 * 64;  // 64 keep words: one lane of wave 0 per word in the scatter
-constexpr int kScanBlock = 1024;
 constexpr uint32_t kNoId = 0xFFFFFFFFu;
 
 std::atomic<int> g_combine{1};  // 0: one global atomic per row (measurements only)
@@ -77,20 +76,6 @@ __device__ __forceinline__ void vote(BestShared& sh, unsigned long long* __restr
         }
     }
     vote_global(votes, n_reads, id, key, rows);
-}
-
-// rows r0 .. r0 + 3 of p (one 16-byte load when the column allows it), `fill` past n
-__device__ __forceinline__ void load4(const uint32_t* __restrict__ p, int64_t r0, int64_t n, bool vec, uint32_t fill,
-                                      uint32_t (&v)[4]) {
-    if (vec && r0 + 4 <= n) {
-        const u32x4_t q = stream_load((const u32x4_t*)(p + r0));
-        v[0] = q.x;
-        v[1] = q.y;
-        v[2] = q.z;
-        v[3] = q.w;
-    } else {
-        for (int k = 0; k < 4; ++k) v[k] = r0 + k < n ? p[r0 + k] : fill;
-    }
 }
 
 template <bool COMBINE>
@@ -189,35 +174,6 @@ k_best_keep(const uint32_t* __restrict__ ids, const uint32_t* __restrict__ score
     }
 }
 
-// exclusive scan of the tile popcounts, one workgroup; the total is n_kept
-__global__ void __launch_bounds__(kScanBlock)
-k_best_scan(const uint32_t* __restrict__ counts, int64_t nt, uint32_t* __restrict__ offs, int64_t* __restrict__ n_kept) {
-    __shared__ uint32_t wtot[kScanBlock / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t carry = 0;
-    for (int64_t base = 0; base < nt; base += kScanBlock) {
-        const int64_t i = base + threadIdx.x;
-        const uint32_t v = i < nt ? counts[i] : 0u;
-        uint32_t s = v;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t u = __shfl_up(s, d);
-            if (lane >= d) s += u;
-        }
-        if (lane == 63) wtot[wave] = s;
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-        for (int k = 0; k < kScanBlock / 64; ++k) {
-            const uint32_t t = wtot[k];
-            if (k < wave) before += t;
-            total += t;
-        }
-        if (i < nt) offs[i] = carry + before + s - v;
-        carry += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *n_kept = (int64_t)carry;
-}
-
 // the set bits of one tile's 64 keep words, ascending, from the tile's offset on
 __global__ void __launch_bounds__(kBlock)
 k_best_scatter(const uint64_t* __restrict__ keep_bits, int64_t n_words, const uint32_t* __restrict__ offs, int64_t cap,
@@ -231,13 +187,8 @@ k_best_scatter(const uint64_t* __restrict__ keep_bits, int64_t n_words, const ui
         const int64_t w = w0 + lane;
         const uint64_t word = w < n_words ? keep_bits[w] : 0ull;
         const uint32_t c = (uint32_t)__popcll(word);
-        uint32_t s = c;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t u = __shfl_up(s, d);
-            if (lane >= d) s += u;
-        }
         words[lane] = word;
-        pre[lane] = s - c;
+        pre[lane] = wave_scan(c, lane) - c;
     }
     __syncthreads();
     const int64_t base = (int64_t)offs[blockIdx.x];
@@ -259,6 +210,9 @@ __global__ void k_best_decode(const unsigned long long* __restrict__ votes, int6
     if (best_score) best_score[c] = (uint32_t)(v >> 32);
 }
 
+// one plane of tile popcounts: its offsets, its total = n_kept
+constexpr auto k_best_scan = k_tile_scan<1, 0>;
+
 struct BestLayout {
     size_t off_votes, off_counts, off_offs, total;
     int64_t tiles;
@@ -267,16 +221,11 @@ struct BestLayout {
 BestLayout best_layout(int64_t n, int64_t n_clusters) {
     BestLayout p;
     p.tiles = (n + kKeepTile - 1) / kKeepTile;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += al(bytes);
-        return at;
-    };
-    p.off_votes = take((size_t)n_clusters * 8);
-    p.off_counts = take((size_t)p.tiles * 4);
-    p.off_offs = take((size_t)p.tiles * 4);
-    p.total = o;
+    Carve c;
+    p.off_votes = c.take((size_t)n_clusters * 8);
+    p.off_counts = c.take((size_t)p.tiles * 4);
+    p.off_offs = c.take((size_t)p.tiles * 4);
+    p.total = c.total;
     return p;
 }
 
@@ -343,12 +292,17 @@ int launch_cluster_best_rows(const uint32_t* ids, const uint32_t* score, int64_t
     return ROGTK_OK;
 }
 
+int check_sizes(const char* name, int64_t n, int64_t n_clusters) {
+    if (int rc = check_rows(name, n)) return rc;
+    ROGTK_REQUIRE(n_clusters >= 0 && n_clusters < (1ll << 32) - 1, ROGTK_E_INVALID,
+                  "%s: n_clusters %lld outside 0..2^32-2", name, (long long)n_clusters);
+    return ROGTK_OK;
+}
+
 // the argument rules of both levels (include/rogtk_dedup.h), before any device work
 int check_best(const char* name, const uint32_t* cluster_id, int64_t n, int64_t n_clusters, const int64_t* best_row,
                const uint64_t* keep_bits, const int64_t* kept_rows, const int64_t* n_kept) {
-    ROGTK_REQUIRE(n >= 0 && n < (1ll << 31), ROGTK_E_INVALID, "%s: n %lld outside 0..2^31-1", name, (long long)n);
-    ROGTK_REQUIRE(n_clusters >= 0 && n_clusters < (1ll << 32) - 1, ROGTK_E_INVALID,
-                  "%s: n_clusters %lld outside 0..2^32-2", name, (long long)n_clusters);
+    if (int rc = check_sizes(name, n, n_clusters)) return rc;
     ROGTK_REQUIRE(n == 0 || cluster_id, ROGTK_E_INVALID, "%s: cluster_id is NULL", name);
     ROGTK_REQUIRE(n == 0 || keep_bits, ROGTK_E_INVALID, "%s: keep_bits is NULL", name);
     ROGTK_REQUIRE(n_clusters == 0 || best_row, ROGTK_E_INVALID, "%s: best_row is NULL", name);
@@ -358,31 +312,18 @@ int check_best(const char* name, const uint32_t* cluster_id, int64_t n, int64_t 
     return ROGTK_OK;
 }
 
-// one device allocation of a host call, released on every way out
-struct HostCallMem {
-    uint8_t* p = nullptr;
-    ~HostCallMem() {
-        if (p) (void)hipFree(p);
-    }
-};
-
 }  // namespace
 }  // namespace rogtk
 
 // ------------------------------------------------------------------ C ABI
-// The entries live in a library of their own (rogtk_amd/_dedup/librogtk_dedup.so), which links
-// librogtk_hip.so for the shared error string (rogtk_last_error); librogtk_hip.so itself is
-// built exactly as without this file.
+// The entries live in a library of their own, rogtk_amd/_dedup/librogtk_dedup.so.
 using namespace rogtk;
 
 extern "C" {
 
 int rogtk_cluster_best_temp_bytes(int64_t n, int64_t n_clusters, int64_t* bytes) {
     ROGTK_REQUIRE(bytes, ROGTK_E_INVALID, "cluster_best_temp_bytes: NULL bytes");
-    ROGTK_REQUIRE(n >= 0 && n < (1ll << 31), ROGTK_E_INVALID, "cluster_best_temp_bytes: n %lld outside 0..2^31-1",
-                  (long long)n);
-    ROGTK_REQUIRE(n_clusters >= 0 && n_clusters < (1ll << 32) - 1, ROGTK_E_INVALID,
-                  "cluster_best_temp_bytes: n_clusters %lld outside 0..2^32-2", (long long)n_clusters);
+    if (int rc = check_sizes("cluster_best_temp_bytes", n, n_clusters)) return rc;
     *bytes = cluster_best_temp(n, n_clusters);
     return ROGTK_OK;
 }
@@ -415,52 +356,31 @@ int rogtk_cluster_best_rows_host(const uint32_t* cluster_id, const uint32_t* sco
     if (int rc = check_best("cluster_best_rows_host", cluster_id, n, n_clusters, best_row, keep_bits, kept_rows,
                             n_kept))
         return rc;
-    int devices = 0;
-    if (hipGetDeviceCount(&devices) != hipSuccess || devices <= 0) {
-        set_error("no HIP device available (librogtk_dedup needs an MI355X / gfx950 GPU)");
-        return ROGTK_E_NODEVICE;
-    }
     // one allocation, the whole call on the default stream: ids, scores, the outputs, temp
     const int64_t cap = std::min(n, n_clusters), words = (n + 63) / 64;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += al(bytes);
-        return at;
-    };
-    const size_t o_ids = take((size_t)n * 4), o_score = take((size_t)n * 4), o_row = take((size_t)n_clusters * 8),
-                 o_bs = take((size_t)n_clusters * 4), o_reads = take((size_t)n_clusters * 4),
-                 o_keep = take((size_t)words * 8), o_kept = take((size_t)cap * 8), o_nk = take(8),
-                 o_temp = take((size_t)cluster_best_temp(n, n_clusters));
-    HostCallMem m;
-    ROGTK_HIP_CHECK(hipMalloc((void**)&m.p, o));
-    uint8_t* d = m.p;
-    if (n > 0) {
-        ROGTK_HIP_CHECK(hipMemcpy(d + o_ids, cluster_id, (size_t)n * 4, hipMemcpyHostToDevice));
-        if (score) ROGTK_HIP_CHECK(hipMemcpy(d + o_score, score, (size_t)n * 4, hipMemcpyHostToDevice));
-    }
-    if (int rc = launch_cluster_best_rows((const uint32_t*)(d + o_ids), score ? (const uint32_t*)(d + o_score) : nullptr,
-                                          n, n_clusters, (int64_t*)(d + o_row), (uint32_t*)(d + o_bs),
-                                          (uint32_t*)(d + o_reads), (uint64_t*)(d + o_keep),
-                                          n_kept ? (int64_t*)(d + o_kept) : nullptr,
-                                          n_kept ? (int64_t*)(d + o_nk) : nullptr, d + o_temp, nullptr))
+    HostCall m;
+    const size_t o_ids = m.take((size_t)n * 4), o_score = m.take((size_t)n * 4), o_row = m.take((size_t)n_clusters * 8),
+                 o_bs = m.take((size_t)n_clusters * 4), o_reads = m.take((size_t)n_clusters * 4),
+                 o_keep = m.take((size_t)words * 8), o_kept = m.take((size_t)cap * 8), o_nk = m.take(8),
+                 o_temp = m.take((size_t)cluster_best_temp(n, n_clusters));
+    if (int rc = m.open("librogtk_dedup")) return rc;
+    if (int rc = m.in(o_ids, cluster_id, (size_t)n * 4)) return rc;
+    if (int rc = m.in(o_score, score, (size_t)n * 4)) return rc;
+    if (int rc = launch_cluster_best_rows(m.at<uint32_t>(o_ids), score ? m.at<uint32_t>(o_score) : nullptr, n,
+                                          n_clusters, m.at<int64_t>(o_row), m.at<uint32_t>(o_bs),
+                                          m.at<uint32_t>(o_reads), m.at<uint64_t>(o_keep),
+                                          n_kept ? m.at<int64_t>(o_kept) : nullptr,
+                                          n_kept ? m.at<int64_t>(o_nk) : nullptr, m.at<void>(o_temp), nullptr))
         return rc;
-    // blocking copies on the default stream: ordered behind the kernels
-    if (n_clusters > 0) {
-        ROGTK_HIP_CHECK(hipMemcpy(best_row, d + o_row, (size_t)n_clusters * 8, hipMemcpyDeviceToHost));
-        if (best_score)
-            ROGTK_HIP_CHECK(hipMemcpy(best_score, d + o_bs, (size_t)n_clusters * 4, hipMemcpyDeviceToHost));
-        if (n_reads) ROGTK_HIP_CHECK(hipMemcpy(n_reads, d + o_reads, (size_t)n_clusters * 4, hipMemcpyDeviceToHost));
-    }
-    if (words > 0) ROGTK_HIP_CHECK(hipMemcpy(keep_bits, d + o_keep, (size_t)words * 8, hipMemcpyDeviceToHost));
-    if (n_kept) {
-        ROGTK_HIP_CHECK(hipMemcpy(n_kept, d + o_nk, 8, hipMemcpyDeviceToHost));
-        ROGTK_REQUIRE(*n_kept >= 0 && *n_kept <= cap, ROGTK_E_HIP, "cluster_best_rows_host: n_kept %lld outside 0..%lld",
-                      (long long)*n_kept, (long long)cap);
-        if (kept_rows && *n_kept > 0)
-            ROGTK_HIP_CHECK(hipMemcpy(kept_rows, d + o_kept, (size_t)*n_kept * 8, hipMemcpyDeviceToHost));
-    }
-    return ROGTK_OK;
+    if (int rc = m.out(best_row, o_row, (size_t)n_clusters * 8)) return rc;
+    if (int rc = m.out(best_score, o_bs, (size_t)n_clusters * 4)) return rc;
+    if (int rc = m.out(n_reads, o_reads, (size_t)n_clusters * 4)) return rc;
+    if (int rc = m.out(keep_bits, o_keep, (size_t)words * 8)) return rc;
+    if (!n_kept) return ROGTK_OK;
+    if (int rc = m.out(n_kept, o_nk, 8)) return rc;
+    ROGTK_REQUIRE(*n_kept >= 0 && *n_kept <= cap, ROGTK_E_HIP, "cluster_best_rows_host: n_kept %lld outside 0..%lld",
+                  (long long)*n_kept, (long long)cap);
+    return m.out(kept_rows, o_kept, (size_t)*n_kept * 8);
 }
 
 }  // extern "C"

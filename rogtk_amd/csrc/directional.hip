@@ -201,21 +201,16 @@ int codes_layout(int64_t m, int L, CodesLayout* p) {
     size_t sb = 0;
     ROGTK_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, (const uint32_t*)nullptr, (uint32_t*)nullptr,
                                                      (int)m1));
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += al(bytes);
-        return at;
-    };
-    p->off_ctrl = take(kCtrlWords * 4);
-    p->off_best = take((size_t)m1 * 8);
-    p->off_deg = take((size_t)m1 * 4);
-    p->off_flag = take((size_t)m1 * 4);
-    p->off_rank = take((size_t)m1 * 4);
-    p->off_adj = take((size_t)m1 * 4 * (size_t)(3 * L));
+    Carve c;
+    p->off_ctrl = c.take(kCtrlWords * 4);
+    p->off_best = c.take((size_t)m1 * 8);
+    p->off_deg = c.take((size_t)m1 * 4);
+    p->off_flag = c.take((size_t)m1 * 4);
+    p->off_rank = c.take((size_t)m1 * 4);
+    p->off_adj = c.take((size_t)m1 * 4 * (size_t)(3 * L));
     p->scan_bytes = sb;
-    p->off_scan = take(sb);
-    p->total = o;
+    p->off_scan = c.take(sb);
+    p->total = c.total;
     return ROGTK_OK;
 }
 

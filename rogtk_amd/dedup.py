@@ -25,9 +25,8 @@ import numpy as np
 import pyarrow as pa
 
 from . import _lib
-from .columns import as_u32
+from .columns import NO_ID, as_u32, current_stream, dev_ptr, device_temp, is_tensor, largest_plus_one, u32_tensor
 
-NO_ID = 0xFFFFFFFF
 BEST_FIELDS = ("best_row", "best_score", "n_reads")
 
 
@@ -48,10 +47,6 @@ def geometry() -> dict:
     out = (ctypes.c_int64 * 4)()
     _lib.call("rogtk_cluster_best_geometry", out)
     return {"select_tile": int(out[0]), "keep_tile": int(out[1]), "slots": int(out[2]), "probes": int(out[3])}
-
-
-def _is_tensor(x) -> bool:
-    return type(x).__module__.split(".")[0] == "torch"
 
 
 def _best_rows_host(cid: np.ndarray, sc: Optional[np.ndarray], k: int) -> DedupResult:
@@ -80,39 +75,25 @@ def _best_rows_device(cid, score, k: int) -> DedupResult:
     keep is the bitmap as int64 words."""
     import torch
 
-    u32 = (torch.int32, torch.uint32)
-    if cid.dim() != 1:
-        raise ValueError(f"cluster_id must be 1-D, got shape {tuple(cid.shape)}")
-    if cid.dtype not in u32 or not cid.is_contiguous():
-        raise ValueError("cluster_id must be a contiguous int32 / uint32 device tensor (the u32 bits)")
-    n = cid.numel()
+    u32_tensor(cid, "cluster_id")
     if score is not None:
-        if not _is_tensor(score) or score.device != cid.device:
-            raise ValueError("score must be a tensor on cluster_id's device")
-        if score.dtype not in u32 or not score.is_contiguous():
-            raise ValueError("score must be a contiguous int32 / uint32 device tensor (the u32 bits)")
-        if tuple(score.shape) != (n,):
-            raise ValueError(f"score has shape {tuple(score.shape)}, cluster_id has {n} rows")
-    dev = cid.device
+        u32_tensor(score, "score", cid, "cluster_id")
+    n, dev = cid.numel(), cid.device
     if k < 0:
-        ids = cid.view(torch.int32).to(torch.int64) & NO_ID
-        ids = ids[ids != NO_ID]
-        k = int(ids.max().item()) + 1 if ids.numel() else 0
+        k = largest_plus_one(cid)
     if not 0 <= k < NO_ID:
         raise ValueError(f"n_clusters {k} outside 0..2^32-2")
     with torch.cuda.device(dev):
-        tb = ctypes.c_int64(0)
-        _lib.call("rogtk_cluster_best_temp_bytes", n, k, ctypes.byref(tb))
-        temp = torch.empty(tb.value, dtype=torch.uint8, device=dev)
+        temp = device_temp("rogtk_cluster_best_temp_bytes", n, k, device=dev)
         best_row = torch.empty(k, dtype=torch.int64, device=dev)
         best_score = torch.empty(k, dtype=torch.int32, device=dev)
         n_reads = torch.empty(k, dtype=torch.int32, device=dev)
         words = torch.empty((n + 63) // 64, dtype=torch.int64, device=dev)
         kept = torch.empty(min(n, k), dtype=torch.int64, device=dev)
         n_kept = torch.empty(1, dtype=torch.int64, device=dev)
-        p = lambda t: None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())
-        _lib.call("rogtk_cluster_best_rows", p(cid), p(score), n, k, p(best_row), p(best_score), p(n_reads), p(words),
-                  p(kept), p(n_kept), p(temp), tb.value, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.call("rogtk_cluster_best_rows", *map(dev_ptr, (cid, score)), n, k,
+                  *map(dev_ptr, (best_row, best_score, n_reads, words, kept, n_kept, temp)), temp.numel(),
+                  current_stream())
         m = int(n_kept.item())
     best = {"best_row": best_row, "best_score": best_score, "n_reads": n_reads}
     return DedupResult(words, kept[:m], best, m, None, k)
@@ -124,14 +105,13 @@ def cluster_best_rows(cluster_id, score=None, n_clusters: int = -1) -> DedupResu
     is skipped. score: one u32 per row, absent = all 0. n_clusters < 0: 1 + the largest id other
     than 0xFFFFFFFF (0 if none). Host arrays (numpy / Arrow) give Arrow out; torch device
     tensors give torch tensors out (keep as int64 bitmap words, best as a dict of tensors)."""
-    if _is_tensor(cluster_id):
+    if is_tensor(cluster_id):
         return _best_rows_device(cluster_id, score, int(n_clusters))
     cid = as_u32(cluster_id, "cluster_id", nulls_to=NO_ID)
     sc = None if score is None else as_u32(score, "score", rows=cid.size)
     k = int(n_clusters)
     if k < 0:
-        real = cid[cid != NO_ID]
-        k = int(real.max()) + 1 if real.size else 0
+        k = largest_plus_one(cid)
     return _best_rows_host(cid, sc, k)
 
 

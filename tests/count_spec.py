@@ -94,6 +94,22 @@ def same(a: Counts, b: Counts) -> bool:
                                                                       "totals", "indptr"))
 
 
+def bad_u32_tensors(host_column):
+    """Tensors that are no u32 column beside a first int32 tensor of 4 rows on the CPU, each with
+    the words the refusal has to name after the column's name."""
+    import torch
+
+    return [
+        (torch.zeros(3, dtype=torch.int32), "has 3 rows"),                            # another length
+        (torch.zeros(4, dtype=torch.float32), "must be a contiguous int32 / uint32"),  # float
+        (torch.zeros(4, dtype=torch.int64), "must be a contiguous int32 / uint32"),    # not the u32 bits
+        (torch.zeros((4, 1), dtype=torch.int32), "must be 1-D"),                       # not 1-D
+        (torch.zeros(8, dtype=torch.int32)[::2], "must be a contiguous int32 / uint32"),  # not contiguous
+        (torch.zeros(4, dtype=torch.int32, device="meta"), "is on meta"),              # another device
+        (host_column, "must be a torch tensor"),                                       # not a tensor beside tensors
+    ]
+
+
 def random_case(seed: int, n=None):
     """(cell, feature, molecule u32, n_cells, n_features, n_molecules): small id spaces, so triples
     repeat and a molecule id turns up under several features and cells; rows skipped for each of

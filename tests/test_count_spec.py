@@ -246,21 +246,13 @@ def test_python_refusals_are_value_errors_before_any_library_call(monkeypatch):
     import torch
 
     t = torch.tensor([0, 1, 1, 0], dtype=torch.int32)
-    bad_tensors = [
-        torch.zeros(3, dtype=torch.int32),                       # another length
-        torch.zeros(4, dtype=torch.float32),                     # float
-        torch.zeros(4, dtype=torch.int64),                       # not the u32 bits
-        torch.zeros((4, 1), dtype=torch.int32),                  # not 1-D
-        torch.zeros(8, dtype=torch.int32)[::2],                  # not contiguous
-        torch.zeros(4, dtype=torch.int32, device="meta"),        # another device
-        good,                                                    # not a tensor beside tensors
-    ]
-    for bad in bad_tensors:
-        for cols in ((t, bad, t), (t, t, bad)):
-            with pytest.raises(ValueError):
+    bad_tensors = S.bad_u32_tensors(good)  # with the one wording of each fault
+    for bad, wording in bad_tensors:
+        for name, cols in (("feature ", (t, bad, t)), ("molecule ", (t, t, bad))):
+            with pytest.raises(ValueError, match=name + wording):
                 rg.count_matrix(*cols, 2, 2, 2)
-    for bad in bad_tensors[1:5]:
-        with pytest.raises(ValueError):
+    for bad, wording in bad_tensors[1:5]:
+        with pytest.raises(ValueError, match="cell " + wording):
             rg.count_matrix(bad, bad, bad, 2, 2, 2)
 
 

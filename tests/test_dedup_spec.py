@@ -94,6 +94,19 @@ def test_geometry_is_exposed():
     assert g["slots"] & (g["slots"] - 1) == 0 and g["probes"] >= 1
 
 
+def test_temp_bytes_is_the_arithmetic_of_the_design():
+    """the u64 votes of every cluster, then the popcount and the offset of every keep
+    tile, each piece rounded up to 256 bytes (an empty piece takes 256)."""
+    tile = dedup.geometry()["keep_tile"]
+    al = lambda b: (max(b, 1) + 255) // 256 * 256
+    lib = _lib.dedup()
+    b = ctypes.c_int64(0)
+    for n, k in ((0, 0), (1, 1), (tile, 7), (tile + 1, 7), (10_000_000, 93_790)):
+        tiles = (n + tile - 1) // tile
+        assert lib.rogtk_cluster_best_temp_bytes(n, k, ctypes.byref(b)) == _lib.ROGTK_OK
+        assert b.value == al(8 * k) + 2 * al(4 * tiles), (n, k)
+
+
 def _refused(lib, fn, *args, word):
     """The call returns ROGTK_E_INVALID and the message names what was wrong."""
     assert getattr(lib, fn)(*args) == _lib.ROGTK_E_INVALID, (fn, word)
@@ -184,3 +197,17 @@ def test_python_refusals_are_value_errors_before_any_library_call(monkeypatch):
             rg.cluster_best_rows(cid)
     with pytest.raises(ValueError):
         rg.cluster_best_rows(ids, n_clusters=(1 << 32) - 1)
+    # device tensors: the shared checker's one wording per fault (the table of tests/test_count_spec.py)
+    import torch
+
+    from count_spec import bad_u32_tensors
+
+    t = torch.tensor([0, 1, 1, 0], dtype=torch.int32)
+    for bad, wording in bad_u32_tensors(ids):
+        with pytest.raises(ValueError, match="score " + wording):
+            rg.cluster_best_rows(t, bad, 2)
+    for bad, wording in bad_u32_tensors(ids)[1:5]:
+        with pytest.raises(ValueError, match="cluster_id " + wording):
+            rg.cluster_best_rows(bad, None, 2)
+        with pytest.raises(ValueError, match="cluster_id " + wording):
+            rg.cluster_best_rows(bad, bad, 2)

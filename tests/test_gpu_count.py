@@ -433,3 +433,28 @@ def test_barcode_keys_as_the_cell_column(rg):
     sizes = (len(white), 6, 25)
     want = _check_host(rg, keys, feats, mols, sizes)
     assert int(want.totals[1]) == int((keys != NO_ID).sum())
+
+
+@pytest.mark.parametrize("first_chunk", ["distinct", "one_triple"])
+def test_the_tile_scan_carries_across_its_chunks(rg, tile, first_chunk):
+    """More flag tiles than the scan's one workgroup takes at once. distinct: every row its own
+    entry, so the second chunk's offsets are its position. one_triple: the first chunk's sorted
+    positions hold one triple, so the second chunk's entry and molecule offsets are 1."""
+    from rogtk_amd import count
+
+    scan_block = count.geometry()["scan_block"]
+    n = (scan_block + 1) * tile + 5
+    row = np.arange(n, dtype=np.int64)
+    c, f = row // 1000, row % 1000
+    sizes = (int(c[-1]) + 1, 1000, 1 << 20)  # 12 + 10 + 20 bits of key
+    m = row * 7919 % sizes[2]
+    if first_chunk == "one_triple":
+        same = scan_block * tile  # (0, 0, 0) sorts first; behind it (1 + j // 1000, j % 1000) for j = 0, 1, ..
+        c, f, m = c + 1, f.copy(), m.copy()
+        c[:same], f[:same], m[:same] = 0, 0, 0
+        c[same:], f[same:] = 1 + (row[same:] - same) // 1000, (row[same:] - same) % 1000
+    perm = np.random.default_rng(16).permutation(n)
+    want, got = _level1(c[perm], f[perm], m[perm], sizes)  # every output, indptr and totals included
+    entries = n if first_chunk == "distinct" else n - scan_block * tile + 1
+    assert want.totals.tolist() == [entries, n, entries]
+    assert got["totals"].tolist() == [entries, n, entries] and int(got["indptr"][-1]) == entries

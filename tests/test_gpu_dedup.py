@@ -365,3 +365,27 @@ def test_device_entry_matches_the_host_entry(rg, geo):
     assert np.array_equal(got.rows.cpu().numpy(), want.rows)
     assert np.array_equal(got.best["best_row"].cpu().numpy(), want.best_row)
     assert np.array_equal(shifted.rows.cpu().numpy(), S.best_lexsort(ids, None, k).rows)
+
+
+@pytest.mark.parametrize("first_chunk", ["kept", "empty"])
+def test_the_tile_scan_carries_across_its_chunks(rg, geo, first_chunk):
+    """More keep tiles than the scan's one workgroup takes at once: the offsets of the second chunk
+    are the first chunk's total plus their own. empty: the first chunk holds skipped rows only, so
+    it sums to 0 and every kept row lies behind it."""
+    from rogtk_amd import count
+
+    scan_block, tile = count.geometry()["scan_block"], geo["keep_tile"]
+    n = (scan_block + 1) * tile + 5
+    k = (n + 2) // 3
+    ids = (np.arange(n, dtype=np.int64) // 3).astype(np.uint32)  # every tile of every chunk has kept rows
+    if first_chunk == "empty":
+        ids[:scan_block * tile] = k + (ids[:scan_block * tile] & 1)  # k and k + 1: skipped
+    score = (np.arange(n, dtype=np.int64) * 2654435761 >> 7 & 3).astype(np.uint32)
+    want = S.best_lexsort(ids, score, k)
+    first = 0 if first_chunk == "kept" else scan_block * tile
+    assert want.n_kept == k - first // 3 and int(want.rows[0]) >= first and int(want.rows[-1]) >= n - 3
+    run = Level1(n, k)  # a dirty temp
+    got = run(ids, score)
+    run.check(got, want)  # all six outputs, exactly
+    m = int(got["n_kept"][0])
+    assert m == want.n_kept and (np.diff(got["kept"][:m]) > 0).all()

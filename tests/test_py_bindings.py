@@ -301,3 +301,37 @@ def test_the_replaced_helpers_are_gone():
             (api, "_ptr"), (api, "group_keys"), (barcode, "_u32_counts"), (dedup, "_host_u32"), (dedup, "_ptr"),
             (bam, "_np_from")]
     assert [(m.__name__, n) for m, n in gone if hasattr(m, n)] == []
+
+
+# ------------------------------------------------------------------ the side libraries
+def test_each_side_library_is_loaded_once_and_is_its_own():
+    d, c = _lib.dedup(), _lib.count()
+    assert _lib.dedup() is d and _lib.count() is c
+    assert d is not c and d is not _lib.hip() and c is not _lib.hip()
+
+
+def test_call_routes_by_the_prefix_table(monkeypatch):
+    class Recorder:
+        def __init__(self):
+            self.names = []
+
+        def __call__(self):
+            return self
+
+        def __getattr__(self, name):
+            self.names.append(name)
+            return lambda *args: _lib.ROGTK_OK
+
+    rec = {which: Recorder() for which in ("dedup", "count", "hip")}
+    for which, r in rec.items():
+        monkeypatch.setattr(_lib, which, r)  # call() looks the loaders up when it is called
+    sent = {"dedup": ["rogtk_cluster_best_rows", "rogtk_cluster_best_temp_bytes", "rogtk_cluster_best_geometry"],
+            "count": ["rogtk_count_matrix", "rogtk_count_matrix_host", "rogtk_count_matrix_set_phases"],
+            "hip": ["rogtk_cluster_summary_dev", "rogtk_device_count", "rogtk_barcode_count_dev"]}
+    for names in sent.values():
+        for name in names:
+            _lib.call(name, 1, 2)
+    assert {which: r.names for which, r in rec.items()} == sent
+    assert set(_lib.SIDE_LIBS) == {"dedup", "count"}
+    assert _lib.SIDE_LIBS["dedup"] == (_lib.DEDUP_PREFIX, _lib.DEDUP_LIB_PATH)
+    assert _lib.SIDE_LIBS["count"] == (_lib.COUNT_PREFIX, _lib.COUNT_LIB_PATH)
