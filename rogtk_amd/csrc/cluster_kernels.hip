@@ -69,9 +69,11 @@ constexpr int kRoundBatch = 4;
 // tile, 1: <= 16384, e.g. the union bitmap of 2-4 ranks' 10M-read batches)
 // S_REDO: the one local-CC instance launched (chosen from the workspace's previous resolve)
 // does not take this bitmap's tiling: cluster_finish redoes the local and global phases.
-enum StatSlot { S_NDISTINCT = 0, S_NCLUSTERS = 1, S_OVERFLOW = 2, S_REDO = 3, S_ROUNDS = 4, S_P0 = 6,
+// S_DOM: the root the roots scan picked as the dominant cluster's, + 1 (0: none); k_word_label
+// marks that cluster's words in wdom for the assign.
+enum StatSlot { S_NDISTINCT = 0, S_NCLUSTERS = 1, S_OVERFLOW = 2, S_REDO = 3, S_ROUNDS = 4, S_DOM = 5, S_P0 = 6,
                 S_LCAP = 7 };
-// stats (8 x int64; slot 5 unused), round flags (u32 per round) at byte 64
+// stats (8 x int64), round flags (u32 per round) at byte 64
 constexpr int kFlagsOff = 64;
 constexpr int kStatsBytes = kFlagsOff + 4 * kMaxRounds;
 
@@ -1379,6 +1381,58 @@ __device__ __forceinline__ void publish_stats(const unsigned long long* stats, u
     }
 }
 
+// The dominant cluster's root for the assign's bitmap (wdom), picked by one workgroup of the
+// roots scan (f is a star forest there): the most frequent root among kDomSample evenly
+// spaced words (word k * stride: the root of its shared local root, else of its first
+// present code; an empty word gives no sample), ties to the smallest root. A mode that
+// holds less than a quarter of the sample positions is no dominant cluster (0). Any choice
+// is exact: only the share of rows the assign answers from the bitmap depends on it.
+constexpr int kDomSample = kBlock;  // one sample per thread
+// wdom (ClusterLayout::off_wdom): u64 0 = the dominant cluster's dense label or kDomNoLabel,
+// u64 1 unused, then one bit per 64-code word (bit w & 63 of u64 w >> 6): set when every
+// present code of the word belongs to the dominant cluster. Bits of empty words are not
+// defined. 32 KB at L = 12, the largest the assign copies into LDS.
+constexpr int kDomHeader = 2;
+constexpr uint64_t kDomNoLabel = ~0ull;
+constexpr int kDomMaxL = 12;
+
+__device__ __forceinline__ void pick_dominant(const uint32_t* __restrict__ f, const uint32_t* __restrict__ UR,
+                                              const uint4* __restrict__ RT, int64_t words, int64_t max_distinct,
+                                              unsigned long long* dom) {
+    __shared__ uint32_t s_samp[kDomSample];
+    __shared__ unsigned long long s_best[kBlock / 64];
+    const int64_t ns = min<int64_t>(kDomSample, words);
+    const int64_t w = (int64_t)threadIdx.x * (words / ns);
+    uint32_t r = kNone;
+    if ((int64_t)threadIdx.x < ns) {
+        uint32_t i = UR[w];
+        if (i == kNone) {
+            const uint4 e = RT[w];
+            if (rt_word(e)) i = e.z;
+        }
+        if ((int64_t)i < max_distinct) r = f[i];
+    }
+    s_samp[threadIdx.x] = r;
+    __syncthreads();
+    uint32_t cnt = 0;
+    if (r != kNone)
+        for (int k = 0; k < kDomSample; ++k) cnt += s_samp[k] == r;
+    // (count, smallest root) as one key; 0 from the lanes without a sample
+    unsigned long long key = r != kNone ? ((unsigned long long)cnt << 32) | (0xFFFFFFFFu - r) : 0ull;
+#pragma unroll
+    for (int off = 32; off; off >>= 1) {
+        const unsigned long long o = __shfl_xor(key, off);
+        key = o > key ? o : key;
+    }
+    if ((threadIdx.x & 63) == 0) s_best[threadIdx.x >> 6] = key;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < kBlock / 64; ++k) key = s_best[k] > key ? s_best[k] : key;
+        const bool any = (int64_t)(key >> 32) * 4 >= ns && key != 0;
+        *dom = any ? (unsigned long long)(0xFFFFFFFFu - (uint32_t)key) + 1ull : 0ull;
+    }
+}
+
 __device__ __forceinline__ void roots_block(const int64_t bid, const uint32_t* __restrict__ f,
                                             const uint64_t* __restrict__ lroot, int64_t max_distinct,
                                             int64_t rwords, uint64_t* __restrict__ rbits,
@@ -1430,8 +1484,13 @@ __global__ __launch_bounds__(kBlock) void k_roots_scan(const uint32_t* __restric
                                                        int64_t rwords, uint64_t* __restrict__ rbits,
                                                        uint32_t* __restrict__ rpref, uint32_t* rblksum,
                                                        const unsigned long long* stats, unsigned long long* host,
-                                                       unsigned long long epoch) {
+                                                       unsigned long long epoch, int64_t rblocks,
+                                                       const uint4* __restrict__ RT, const uint32_t* __restrict__ UR,
+                                                       int64_t words) {
     if (host && blockIdx.x == 0) publish_stats(stats, host, epoch);
+    // not the publishing workgroup, which has the longest path already
+    if ((int64_t)blockIdx.x == (rblocks > 1 ? 1 : 0))
+        pick_dominant(f, UR, RT, words, max_distinct, const_cast<unsigned long long*>(stats) + S_DOM);
     roots_block(blockIdx.x, f, lroot, max_distinct, rwords, rbits, rpref, rblksum, stats);
 }
 
@@ -1446,9 +1505,11 @@ __global__ __launch_bounds__(kBlock) void k_roots_check(const uint32_t* __restri
                                                         const uint4* __restrict__ RT, const uint32_t* __restrict__ UR,
                                                         int64_t words, int L, int p0, unsigned int* flags, int round,
                                                         uint64_t* active, int64_t active_words) {
-    if ((int64_t)blockIdx.x < rblocks)
+    if ((int64_t)blockIdx.x < rblocks) {
+        if ((int64_t)blockIdx.x == (rblocks > 1 ? 1 : 0))
+            pick_dominant(f, UR, RT, words, max_distinct, const_cast<unsigned long long*>(stats) + S_DOM);
         roots_block(blockIdx.x, f, lroot, max_distinct, rwords, rbits, rpref, rblksum, stats);
-    else
+    } else
         hook_block<true>((int64_t)blockIdx.x - rblocks, RT, UR, words, L, p0, const_cast<uint32_t*>(f), flags,
                                 round, active, active_words, stats);
 }
@@ -1490,7 +1551,8 @@ __global__ __launch_bounds__(kBlock) void k_word_label(const uint32_t* __restric
                                                        int64_t nrb_max = 0, unsigned long long* stats = nullptr,
                                                        const unsigned long long* pstats = nullptr,
                                                        unsigned long long* host = nullptr,
-                                                       unsigned long long epoch = 0) {
+                                                       unsigned long long epoch = 0,
+                                                       uint64_t* __restrict__ wdom = nullptr) {
     extern __shared__ uint32_t s_roff[];
     __shared__ uint32_t s_wave[kBlock / 64];
     if (host && blockIdx.x == 0) publish_stats(pstats, host, epoch);  // after k_roots_check
@@ -1514,6 +1576,10 @@ __global__ __launch_bounds__(kBlock) void k_word_label(const uint32_t* __restric
         __syncthreads();
         rblkoff = s_roff;
     }
+    // the dominant root the roots scan picked (kNone: none) and, for the assign, its label
+    const uint32_t dom = wdom ? (uint32_t)pstats[S_DOM] - 1u : kNone;
+    if (wdom && blockIdx.x == 0 && threadIdx.x == 0)
+        wdom[0] = dom != kNone ? (uint64_t)root_label(dom, rbits, rpref, rblkoff) : kDomNoLabel;
     for (int64_t w = (int64_t)blockIdx.x * kBlock + threadIdx.x; w < words; w += (int64_t)gridDim.x * kBlock) {
         const uint32_t ur = UR[w];
         uint32_t root = kNone;
@@ -1567,6 +1633,13 @@ __global__ __launch_bounds__(kBlock) void k_word_label(const uint32_t* __restric
             }
         }
         wlab[w] = lab;
+        if (wdom) {
+            // one bit per word: it has a label, its root is the dominant one and none of its
+            // present codes is an exception; a ballot makes 64 words' bits (a wave's lanes
+            // hold 64 consecutive words: kBlock and the grid stride are multiples of 64)
+            const uint64_t b = __ballot(lab != kNone && root == dom && !exc);
+            if ((threadIdx.x & 63) == 0) wdom[kDomHeader + (w >> 6)] = b;
+        }
         // the codes the word label does not cover (its exceptions, or all of them when
         // the word stays unlabelled) get their own label (f[i] is their root: they are
         // live); a uniform word (ur != kNone) always has a label
@@ -1602,13 +1675,36 @@ __device__ __forceinline__ uint32_t word_label_of(const uint32_t* __restrict__ w
 // G groups of 4 rows per lane and loop trip (all loads of a trip in flight at once):
 // lane l of a wave owns rows {tile + 256 g + 4 l .. + 3}, so each 16-B load / store
 // instruction of a wave covers 1 KB contiguous.
-template <int MODE, int G>
+// DOM (max_distance 1 with word labels, L <= kDomMaxL; ROGTK_ASSIGN_DOM=0: off): every
+// workgroup first copies the dominant cluster's word bitmap (wdom, dom_words u64 after the
+// header) into LDS; a row whose word has its bit set takes the dominant label without any
+// gather, the other rows go on as above. No dominant cluster (kDomNoLabel): no copy, and
+// every row goes on as above.
+template <int MODE, int G, bool DOM = false>
 __global__ __launch_bounds__(kBlock) void k_assign(const uint32_t* __restrict__ codes,
                                                    const uint64_t* __restrict__ regbits, int64_t n,
                                                    const uint32_t* __restrict__ labelcode,
                                                    const uint32_t* __restrict__ flab,
                                                    const uint4* __restrict__ RT, const uint32_t* __restrict__ wlab,
-                                                   const uint64_t* __restrict__ wexc, uint32_t* __restrict__ out) {
+                                                   const uint64_t* __restrict__ wexc, uint32_t* __restrict__ out,
+                                                   const uint64_t* __restrict__ wdom, int dom_words) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_dom[];  // DOM: dom_words u64 (even, or 1)
+    uint32_t dom_label = 0;
+    bool dom_on = false;
+    if (DOM) {
+        const uint64_t h = wdom[0];
+        dom_on = h != kDomNoLabel;
+        dom_label = (uint32_t)h;
+        if (dom_on) {
+            if (dom_words >= 2) {
+                const uint4* src = reinterpret_cast<const uint4*>(wdom + kDomHeader);
+                for (int i = threadIdx.x; i < dom_words / 2; i += kBlock) reinterpret_cast<uint4*>(s_dom)[i] = src[i];
+            } else if (threadIdx.x < 2) {
+                s_dom[threadIdx.x] = reinterpret_cast<const uint32_t*>(wdom + kDomHeader)[threadIdx.x];
+            }
+            __syncthreads();
+        }
+    }
     constexpr int64_t kTile = 256 * G;  // rows per wave and trip
     const int lane = threadIdx.x & 63;
     const int64_t nwaves = (int64_t)gridDim.x * (kBlock / 64);
@@ -1636,6 +1732,10 @@ __global__ __launch_bounds__(kBlock) void k_assign(const uint32_t* __restrict__ 
             for (int k = 0; k < 4; ++k) {
                 id[g][k] = 0xFFFFFFFFu;
                 if ((reg[g] >> k) & 1u) {
+                    if (DOM && dom_on && ((s_dom[c[g][k] >> 11] >> ((c[g][k] >> 6) & 31u)) & 1u)) {
+                        id[g][k] = dom_label;
+                        continue;
+                    }
                     const uint32_t wl = wlab ? word_label_of(wlab, wexc, c[g][k]) : kNone;
                     id[g][k] = wl != kNone ? wl
                                : MODE == 0 ? labelcode[c[g][k]]
@@ -1696,6 +1796,7 @@ struct WsPtrs {
     uint32_t *rpref, *rblksum, *rblkoff, *labelcode, *ilab;
     uint64_t* active;
     uint64_t* lb;               // look-back flags of k_scan_rt (+ its error word)
+    uint64_t* wdom;             // the dominant cluster's word bitmap (nullptr: L > kDomMaxL)
 };
 
 inline WsPtrs ws_ptrs(const ClusterLayout& cl, uint8_t* ws) {
@@ -1720,6 +1821,7 @@ inline WsPtrs ws_ptrs(const ClusterLayout& cl, uint8_t* ws) {
     p.ilab = cl.label_by_code ? nullptr : (uint32_t*)(ws + cl.off_ilab);
     p.active = (uint64_t*)(ws + cl.off_active);
     p.lb = (uint64_t*)(ws + cl.off_lb);
+    p.wdom = cl.dom_words ? (uint64_t*)(ws + cl.off_wdom) : nullptr;
     return p;
 }
 
@@ -1774,6 +1876,9 @@ int cluster_layout(int L, int64_t max_distinct, ClusterLayout* o) {
     c.off_active = take(2 * std::max<int64_t>(c.active_words, 1) * 8);
     // look-back flags + error word + tagged block totals (k_scan_rt)
     c.off_lb = take((2 * std::max(c.blocks, c.rblocks) + 1) * 8);
+    // the dominant cluster's word bitmap, where the assign's LDS copy takes it (else 0 bytes)
+    c.dom_words = L <= kDomMaxL ? (c.words + 63) / 64 : 0;
+    c.off_wdom = take(c.dom_words ? (kDomHeader + c.dom_words + 1) * 8 : 0);
     c.total = off;
     *o = c;
     return ROGTK_OK;
@@ -1930,7 +2035,8 @@ int enqueue_labels(const ClusterLayout& cl, const WsPtrs& p, hipStream_t s,
         } else {
             ROGTK_TIMED_LAUNCH(K_K_ROOTS, k_roots_scan, dim3((unsigned)cl.rblocks), dim3(kBlock), 0, s, p.f, p.lroot,
                                cl.max_distinct, cl.rwords, p.rbits, p.rpref, p.rblksum,
-                               (const unsigned long long*)p.stats, host_stats, (unsigned long long)epoch);
+                               (const unsigned long long*)p.stats, host_stats, (unsigned long long)epoch, cl.rblocks,
+                               p.RT, p.UR, cl.words);
         }
         if (!lds_off)
             hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(kBlock), 0, s, p.rblksum, cl.rblocks, p.rblkoff, p.stats,
@@ -1953,7 +2059,7 @@ int enqueue_labels(const ClusterLayout& cl, const WsPtrs& p, hipStream_t s,
                            p.rbits, p.rpref, p.rblkoff, p.wpref, p.G, p.labelcode, p.ilab, exc1_on,
                            lds_off ? p.rblksum : nullptr, (int64_t)cl.rblocks, lds_off ? p.stats : nullptr,
                            (const unsigned long long*)p.stats, check_round >= 0 ? host_stats : nullptr,
-                           (unsigned long long)epoch);
+                           (unsigned long long)epoch, p.wdom);
         if (t_resolve_fin && attached_event_taken()) t_resolve_fin = nullptr;
         ROGTK_HIP_CHECK(hipGetLastError());
     }
@@ -2324,15 +2430,30 @@ int enqueue_assign(const ClusterLayout& cl, const WsPtrs& p, int labels, const u
     }();
     constexpr int kGroups = ROGTK_ASSIGN_G;
     const int g = grid_for((n + 4 * kGroups - 1) / (4 * kGroups), cap);
-    if (labels == 2)  // exact ids: the ranks
+    // ROGTK_ASSIGN_DOM=0: the instance without the dominant cluster's bitmap (A/B, tests)
+    static const bool dom_on = [] {
+        const char* e = getenv("ROGTK_ASSIGN_DOM");
+        return !(e && e[0] == '0');
+    }();
+    if (labels == 1 && cl.label_by_code && p.wdom && dom_on) {
+        // the bitmap in LDS (32 KB at L = 12): two workgroups per CU leave the resolve's
+        // local CC its room
+        const int dw = (int)cl.dom_words;
+        hipExtLaunchKernelGGL((k_assign<0, kGroups, true>), dim3(g), dim3(kBlock), (size_t)(dw + (dw & 1)) * 8, s,
+                              prof.start(), prof.stop(), 0, codes, regular_bits, n, p.labelcode, p.D, p.RT, wlab, wexc,
+                              cluster_id, (const uint64_t*)p.wdom, dw);
+    } else if (labels == 2)  // exact ids: the ranks
         hipExtLaunchKernelGGL((k_assign<2, kGroups>), dim3(g), dim3(kBlock), 0, s, prof.start(), prof.stop(), 0, codes,
-                              regular_bits, n, p.labelcode, p.ilab, p.RT, wlab, wexc, cluster_id);
+                              regular_bits, n, p.labelcode, p.ilab, p.RT, wlab, wexc, cluster_id,
+                              (const uint64_t*)nullptr, 0);
     else if (cl.label_by_code)
         hipExtLaunchKernelGGL((k_assign<0, kGroups>), dim3(g), dim3(kBlock), 0, s, prof.start(), prof.stop(), 0, codes,
-                              regular_bits, n, p.labelcode, p.D, p.RT, wlab, wexc, cluster_id);
+                              regular_bits, n, p.labelcode, p.D, p.RT, wlab, wexc, cluster_id,
+                              (const uint64_t*)nullptr, 0);
     else
         hipExtLaunchKernelGGL((k_assign<1, kGroups>), dim3(g), dim3(kBlock), 0, s, prof.start(), prof.stop(), 0, codes,
-                              regular_bits, n, p.labelcode, p.ilab, p.RT, wlab, wexc, cluster_id);
+                              regular_bits, n, p.labelcode, p.ilab, p.RT, wlab, wexc, cluster_id,
+                              (const uint64_t*)nullptr, 0);
     ROGTK_HIP_CHECK(hipGetLastError());
     return ROGTK_OK;
 }

@@ -279,6 +279,10 @@ struct ClusterLayout {
     int64_t off_stats, off_presence, off_bitmap, off_rt, off_wpref, off_blksum, off_blkoff, off_D, off_f, off_ur,
         off_rbits, off_lroot, off_rpref, off_rblksum, off_rblkoff, off_labelcode, off_ilab, off_active,
         active_words, off_lb, total;
+    // the dominant cluster's word bitmap (dom_words u64 behind a 16-byte header; dom_words = 0:
+    // none, the code space is too large for the assign's LDS copy). Last, so that the
+    // regions before it lie where they did.
+    int64_t off_wdom, dom_words;
 };
 int cluster_layout(int L, int64_t max_distinct, ClusterLayout* out);
 
